@@ -15,6 +15,13 @@ request to the shard that owns it inside fixed-size padded sub-batches over
 RCCL send/recv (xGMI) and returns the responses to the submitting rank.
 Per-GPU work is fixed as N grows (2^24 messages and 64K requests per GPU):
 weak scaling.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line (`value`,
+`ms_per_step`, the stage times and rooflines of the timed steps).  `--full`
+adds what takes runs of its own: the response checks of every timed batch,
+one call per batch, the host API, the wire path and signature check, and the
+CPU baseline; without it those keys are null.  `--dump-outputs DIR` writes
+the last timed batch's responses (dump_outputs).
 """
 import argparse
 import ctypes
@@ -42,6 +49,13 @@ def parse():
     p.add_argument("--log2n", type=int, default=24, help="log2 message capacity per GPU")
     p.add_argument("--batch", type=int, default=65536)
     p.add_argument("--fill", type=float, default=0.75)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the side measurements and checks: the response "
+                        "checks of every timed batch, one call per batch, the host API, the wire path "
+                        "and signature check, the CPU baseline (--no-cpu, --host-steps, --wire-steps "
+                        "and --cpu-* apply only here)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed batch's responses to DIR/<name>.npy (dump_outputs)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="CPU baseline instances (host threads); 0 = this process's CPU share")
@@ -164,6 +178,31 @@ def check_batch(torch, r, o):
     bad |= (st < 0) | (st > 7)
     dels = ok & (typ == 4)
     return int(bad.sum()), int(cre.sum()), int(dels.sum())
+
+
+DUMP_ROWS = 8192  # sampled responses: 8192 x 1040 float32 = 34 MB
+
+
+def dump_outputs(path, out, suffix=""):
+    """--dump-outputs: the responses of the last timed batch (n x 1040 bytes,
+    gvs_response layout), as float32 / float64 arrays under `path`:
+    `status` (n status codes), `row_digest` (per response the sum of its bytes
+    weighted 1..61 by position, below 2^24 and so exact in float32: every byte
+    of every response counts), and a fixed, seeded sample of whole responses,
+    `responses_sample` (DUMP_ROWS x 1040 byte values) at rows `sample_rows`.
+    The inputs are seeded, so two builds can be compared file by file."""
+    import numpy as np
+    o = out.cpu().numpy()
+    n = o.shape[0]
+    rows = np.sort(np.random.default_rng(0x6772617065).choice(n, min(n, DUMP_ROWS), replace=False))
+    w = (np.arange(o.shape[1]) % 61 + 1).astype(np.float32)
+    arrays = {"status": o[:, 1024:1028].copy().view(np.int32).reshape(n).astype(np.float32),
+              "row_digest": np.concatenate([o[i:i + 8192].astype(np.float32) @ w for i in range(0, n, 8192)]),
+              "responses_sample": o[rows].astype(np.float32),
+              "sample_rows": rows.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
 
 
 def host_cpu():
@@ -523,6 +562,11 @@ def predict_shards(a, torch, dev, json_out):
 
 def main():
     a = parse()
+    if not a.full:
+        # a plain run measures the headline figure only: set up, warm up, time
+        # the steps, dump the outputs if asked, print the line
+        a.host_steps = a.wire_steps = 0
+        a.no_cpu = True
     # RCCL prints a version banner on stdout at communicator creation; keep
     # stdout for the single JSON line and send everything else to stderr
     json_out = os.fdopen(os.dup(1), "w")
@@ -570,9 +614,10 @@ def main():
     known = prefill(torch, store, dev, B, int(N * a.fill), pool, g, 1_700_000_000,
                     per_batch=B - a.expiry)
     n_host = a.host_steps + (3 if a.host_steps else 0)  # pipelined, two one by one, one warm-up
-    batches = gen_batches(torch, dev, B, a.warmup + a.steps + n_host + a.steps, known, pool, g,
+    n_obo = a.steps if a.full else 0
+    batches = gen_batches(torch, dev, B, a.warmup + a.steps + n_host + n_obo, known, pool, g,
                           1_800_000_000)
-    one_by_one = batches[-a.steps:]  # the same API one call per batch, timed after the checks
+    one_by_one = batches[len(batches) - n_obo:]  # the same API one call per batch, timed after the checks
     d_out = torch.empty((B, 1040), dtype=torch.uint8, device=dev)
     nreq = B - a.expiry  # requests per batch (the expiry deletes take the last X slots)
     # the timed batches back to back in one device array, submitted in one
@@ -605,31 +650,35 @@ def main():
     st = store.stats()
     d_out = d_outs[-1]
     statuses = torch.bincount(d_out[:, 1024].to(torch.int64), minlength=9)[:9].tolist()
-    # response properties of every timed batch, and message conservation
-    viol, n_cre, n_del = 0, 0, 0
-    for i in range(a.steps):
-        v, c, d = check_batch(torch, batches[a.warmup + i][:nreq], d_outs[i][:nreq])
-        viol, n_cre, n_del = viol + v, n_cre + c, n_del + d
-    expired = msgs_before + n_cre - n_del - st["messages"]
-    checks = {"batches": a.steps, "violations": viol, "creates_ok": n_cre, "deletes_ok": n_del,
-              "messages_before": msgs_before, "messages_after": st["messages"],
-              "conserved": expired == 0 if not a.expiry else expired >= 0,
-              "expired": expired}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, d_out, f"_rank{rank}" if world > 1 else "")
+    checks, per_batch_api = None, None
+    if a.full:
+        # response properties of every timed batch, and message conservation
+        viol, n_cre, n_del = 0, 0, 0
+        for i in range(a.steps):
+            v, c, d = check_batch(torch, batches[a.warmup + i][:nreq], d_outs[i][:nreq])
+            viol, n_cre, n_del = viol + v, n_cre + c, n_del + d
+        expired = msgs_before + n_cre - n_del - st["messages"]
+        checks = {"batches": a.steps, "violations": viol, "creates_ok": n_cre, "deletes_ok": n_del,
+                  "messages_before": msgs_before, "messages_after": st["messages"],
+                  "conserved": expired == 0 if not a.expiry else expired >= 0,
+                  "expired": expired}
 
-    # for comparison: one gvs_process_batch_device call per batch (each call
-    # waits for its batch's verdict before the next is enqueued)
-    store.synchronize()
-    gdist.barrier(ri)
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for x in one_by_one:
-        store.process_batch_device(x.data_ptr(), nreq, d_out.data_ptr())
-    store.synchronize()
-    torch.cuda.synchronize(dev)
-    t_obo = gdist.max_over_ranks(ri, time.perf_counter() - t0, device=dev)
-    per_batch_api = {"value": world * nreq * a.steps / t_obo, "unit": "req/s",
-                     "ms_per_batch": t_obo / a.steps * 1e3,
-                     "api": "gvs_process_batch_device, one call (and one host round trip) per batch"}
+        # for comparison: one gvs_process_batch_device call per batch (each call
+        # waits for its batch's verdict before the next is enqueued)
+        store.synchronize()
+        gdist.barrier(ri)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for x in one_by_one:
+            store.process_batch_device(x.data_ptr(), nreq, d_out.data_ptr())
+        store.synchronize()
+        torch.cuda.synchronize(dev)
+        t_obo = gdist.max_over_ranks(ri, time.perf_counter() - t0, device=dev)
+        per_batch_api = {"value": world * nreq * a.steps / t_obo, "unit": "req/s",
+                         "ms_per_batch": t_obo / a.steps * 1e3,
+                         "api": "gvs_process_batch_device, one call (and one host round trip) per batch"}
 
     host_path = None
     if a.host_steps:
@@ -783,6 +832,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": elapsed / a.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",

@@ -32,3 +32,52 @@ def test_oracle_responses_pass_and_corruption_is_caught():
     bad[fail[0], 200] ^= 1  # ... and of a failure record
     v2, _, _ = bench.check_batch(torch, r, bad)
     assert v2 == 2
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float arrays within 64 MB, the same from call to call,
+    and a changed byte of any response changes `row_digest`."""
+    g = torch.Generator()
+    g.manual_seed(5)
+    n = 2 * bench.DUMP_ROWS + 3  # more rows than the sample holds, not a multiple of the digest's chunk
+    o = torch.randint(0, 256, (n, 1040), dtype=torch.uint8, generator=g)
+    o[:, 1025:1028] = 0
+    bench.dump_outputs(str(tmp_path / "a"), o)
+    bench.dump_outputs(str(tmp_path / "b"), o)
+    assert all(p.suffix == ".npy" for p in (tmp_path / "a").iterdir())
+    names = sorted(p.stem for p in (tmp_path / "a").iterdir())
+    assert names == ["responses_sample", "row_digest", "sample_rows", "status"]
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    # at the benchmark's batch size too: 64K statuses and digests beside the fixed sample
+    assert a["responses_sample"].nbytes + 65536 * (4 + 4) + bench.DUMP_ROWS * 8 <= 64 << 20
+    for k in names:
+        assert np.array_equal(a[k], np.load(tmp_path / "b" / f"{k}.npy")), k
+    rows = a["sample_rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and len(np.unique(rows)) == len(rows)
+    h = o.numpy()
+    assert np.array_equal(a["responses_sample"], h[rows].astype(np.float32))
+    assert np.array_equal(a["status"], h[:, 1024].astype(np.float32))
+    w = np.arange(1040) % 61 + 1
+    assert np.array_equal(a["row_digest"], (h.astype(np.int64) @ w).astype(np.float32))
+    o2 = o.clone()
+    o2[n - 1, 517] ^= 1
+    bench.dump_outputs(str(tmp_path / "c"), o2)
+    c = np.load(tmp_path / "c" / "row_digest.npy")
+    assert (c != a["row_digest"]).nonzero()[0].tolist() == [n - 1]
+
+
+def test_plain_run_options():
+    """--full is off by default; the side measurements' options parse either way."""
+    import sys
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+        sys.argv += ["--full", "--dump-outputs", "d", "--no-cpu", "--host-steps", "0"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "d" and a.no_cpu and a.host_steps == 0
+    finally:
+        sys.argv = argv

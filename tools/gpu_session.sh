@@ -28,22 +28,22 @@ step() {  # step NAME SECONDS CMD...
 PT="python3 -u -m pytest -v --timeout 600 --timeout-method thread -p no:cacheprovider"
 tests() { step gpu_tests 600 $PT tests -m gpu --ignore=tests/test_oblivious.py --ignore=tests/test_timing.py "$@"; }
 timing() { step timing_c3 300 $PT tests/test_timing.py; cp gpurun_out/timing_c3.txt "$O/" 2>/dev/null; }
-bench() { step bench 300 python3 bench.py; }
+bench() { step bench 300 python3 bench.py --full; }
 SEALT="tests/test_gpu_seal.py tests/test_gpu_oram.py tests/test_gpu_omap.py tests/test_gpu_epoch.py"
 case "$2" in
   seal) step seal_tests 600 $PT $SEALT ;;
   sealobl) step seal_tests 600 $PT $SEALT && \
     step oblivious_auth 900 $PT tests/test_oblivious.py -k "auth and not oram_auth and not omap_auth" && \
-    step bench_auth 400 python3 bench.py --auth --no-cpu --steps 5 ;;
+    step bench_auth 400 python3 bench.py --full --auth --no-cpu --steps 5 ;;
   plaintime)  # the plain pass's timing and counters, then the C3 bench line
     step timing_store 600 $PT tests/test_timing.py -k "independent_of_mix and not sealed and not routed"
     cp gpurun_out/timing_c3_store.txt "$O/" 2>/dev/null
     step oblivious_plain 600 $PT tests/test_oblivious.py -k "plain"
-    step bench 400 python3 bench.py --no-cpu ;;
+    step bench 400 python3 bench.py --full --no-cpu ;;
   sealperf)  # the sealed tests, the sealed bench at 12 and 8 waves
     step seal_tests 600 $PT $SEALT
-    step bench_auth12 400 python3 bench.py --auth --no-cpu --steps 5 --sealed-waves 12
-    step bench_auth8 400 python3 bench.py --auth --no-cpu --steps 5 --sealed-waves 8 ;;
+    step bench_auth12 400 python3 bench.py --full --auth --no-cpu --steps 5 --sealed-waves 12
+    step bench_auth8 400 python3 bench.py --full --auth --no-cpu --steps 5 --sealed-waves 8 ;;
   contract)  # every counter and timing shape
     step oblivious_all 1200 $PT tests/test_oblivious.py
     step timing_all 900 $PT tests/test_timing.py
@@ -67,7 +67,7 @@ case "$2" in
     tests && \
     step obl_routed 600 $PT tests/test_oblivious.py -k "routed" && \
     step timing_rs 600 $PT tests/test_timing.py -k "routed or (independent_of_mix and not sealed)" && \
-    step bench 400 python3 bench.py --no-cpu
+    step bench 400 python3 bench.py --full --no-cpu
     cp gpurun_out/timing_c3_*.txt gpurun_out/oblivious_*_routed.txt "$O/" 2>/dev/null ;;
   timeab)  # routed and store timing for the in-tree build and each ab/ library in TIMEAB
     step timing_rs_base 600 $PT tests/test_timing.py -k "routed or (independent_of_mix and not sealed)"
@@ -132,7 +132,7 @@ case "$2" in
     tests && \
     step timing_store 600 $PT tests/test_timing.py -k "independent_of_mix and not sealed and not routed" && \
     step obl_plain 600 $PT tests/test_oblivious.py -k "plain" && \
-    step bench 400 python3 bench.py --no-cpu
+    step bench 400 python3 bench.py --full --no-cpu
     cp gpurun_out/timing_c3_store*.txt gpurun_out/oblivious_*_plain.txt "$O/" 2>/dev/null ;;
   ttime)  # the GPU suite without counters/timing, then every timing shape with per-test durations
     tests && \
@@ -141,7 +141,7 @@ case "$2" in
   timeall)  # every timing shape, then the default bench line
     step timing_all 1000 $PT tests/test_timing.py
     cp gpurun_out/timing_c3_*.txt "$O/" 2>/dev/null
-    step bench 400 python3 bench.py --no-cpu ;;
+    step bench 400 python3 bench.py --full --no-cpu ;;
   routed)  # the sharded path: parity, counters, timing
     step sharded_tests 600 $PT tests/test_gpu_sharded.py
     step obl_routed 900 $PT tests/test_oblivious.py -k "routed"
@@ -163,8 +163,8 @@ case "$2" in
     step driver_x 1100 python3 -u -m pytest tests/ -x -q -m gpu --timeout 300 --timeout-method thread
     cp gpurun_out/oblivious_*.txt gpurun_out/timing_c3_*.txt "$O/" 2>/dev/null
     step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
-    step bench 400 python3 bench.py
-    step bench_auth 400 python3 bench.py --auth --no-cpu --steps 5 ;;
+    step bench 400 python3 bench.py --full
+    step bench_auth 400 python3 bench.py --full --auth --no-cpu --steps 5 ;;
   tests) tests ;;
   timing) timing ;;
   bench) bench ;;
@@ -194,22 +194,22 @@ case "$2" in
     done
     rm -rf "$O/pmc_fetch" "$O/pmc_write" ;;
   prof)  # HBM traffic of k_rpass2 (two PMC passes), kernel stats, auth and expiry lines
-    step pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d "$O/pmc_fetch" -o run --output-format csv -- python3 bench.py --no-cpu --steps 5 --warmup 1
-    step pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d "$O/pmc_write" -o run --output-format csv -- python3 bench.py --no-cpu --steps 5 --warmup 1
+    step pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d "$O/pmc_fetch" -o run --output-format csv -- python3 bench.py --full --no-cpu --steps 5 --warmup 1
+    step pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d "$O/pmc_write" -o run --output-format csv -- python3 bench.py --full --no-cpu --steps 5 --warmup 1
     python3 tools/traffic_from_pmc.py "$O/pmc_fetch" "$O/pmc_write" 24 65536 k_rpass2s > "$O/traffic_latest.json" && cp "$O/traffic_latest.json" profiles/traffic_latest.json
     rm -rf "$O/pmc_fetch" "$O/pmc_write"
-    step kstats 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python3 bench.py --no-cpu
+    step kstats 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python3 bench.py --full --no-cpu
     find "$O/prof" -name "*kernel_stats.csv" -exec cp {} "$O/kernel_stats.csv" \;
     find "$O/prof" -name "*kernel_trace.csv" -delete
-    step bench_full 300 python3 bench.py
-    step pmc_valu 600 rocprofv3 --pmc SQ_INSTS_VALU -d "$O/pmc_valu" -o run --output-format csv -- python3 bench.py --auth --no-cpu --steps 5 --warmup 1
+    step bench_full 300 python3 bench.py --full
+    step pmc_valu 600 rocprofv3 --pmc SQ_INSTS_VALU -d "$O/pmc_valu" -o run --output-format csv -- python3 bench.py --full --auth --no-cpu --steps 5 --warmup 1
     python3 tools/valu_from_pmc.py "$O/pmc_valu" 24 65536 k_spass > "$O/valu_auth_latest.json" && cp "$O/valu_auth_latest.json" profiles/
     step predict 600 python3 bench.py --predict-shards 8 --steps 3 --warmup 1
     grep '^{"metric": "predicted' "$O/predict.log" | tail -1 > "$O/scale_prediction.json" && \
       python3 -c "import json; d=json.load(open('$O/scale_prediction.json')); json.dump(d, open('profiles/scale_prediction.json','w'), indent=1)"
     rm -rf "$O/pmc_valu"
-    step bench_auth 600 python3 bench.py --auth --no-cpu --steps 5
-    step bench_expiry 300 python3 bench.py --expiry 1024 --no-cpu
+    step bench_auth 600 python3 bench.py --full --auth --no-cpu --steps 5
+    step bench_expiry 300 python3 bench.py --full --expiry 1024 --no-cpu
     step kstats_auth 400 rocprofv3 --kernel-trace --stats -d "$O/ka" -o run --output-format csv -- \
       python3 bench.py --auth --no-cpu --host-steps 0 --wire-steps 0 --steps 5 --warmup 2
     find "$O/ka" -name "*kernel_stats.csv" -exec cp {} "$O/kernel_stats_auth.csv" \;
