@@ -12,8 +12,9 @@ SRCS := grapevine_amd/csrc/gvs_engine.hip
 HDRS := $(wildcard grapevine_amd/csrc/*.h) include/gvstore.h include/gvstore_test.h
 
 SRHOST := tests/libsrhost.so
+EDHOST := tests/libedhost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -25,11 +26,16 @@ $(TESTLIB): $(SRCS) $(HDRS)
 $(SRHOST): tests/sr_host.cpp grapevine_amd/csrc/gvs_sr25519.h grapevine_amd/csrc/gvs_device.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/sr_host.cpp
 
+# the device Ed25519 check (SHA-512, decode, the whole verification) built for
+# the CPU (tests/test_ed_host.py)
+$(EDHOST): tests/ed_host.cpp grapevine_amd/csrc/gvs_ed25519.h grapevine_amd/csrc/gvs_sr25519.h grapevine_amd/csrc/gvs_device.h
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/ed_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

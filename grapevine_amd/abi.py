@@ -96,7 +96,11 @@ WIRE_REQUEST_BYTES, WIRE_RESPONSE_BYTES, WIRE_SLOT_MAX = 1099, 1042, 2048
 WIRE_OK, WIRE_DECODE_ERROR, WIRE_BAD_FIELD, WIRE_BAD_SIGNATURE = 0, 1, 2, 3
 
 COMM_ID_BYTES = 128
-FLAG_AUTH_STORAGE = 1  # GVS_FLAG_AUTH_STORAGE: AES-CTR + BLAKE2b sealed tables
+# GVS_FLAG_AUTH_STORAGE: AES-CTR sealed tables; rows of tables 0, 1, 2 and
+# 0x100 carry an AES header and the NH/L3 row hash, the map directory (table 3)
+# a BLAKE2b XOR-MAC (gvs_crypto.h)
+FLAG_AUTH_STORAGE = 1
+FLAG_ED25519_AUTH = 2  # GVS_FLAG_ED25519_AUTH: the wire path checks Ed25519 challenge signatures
 ERR_INTEGRITY = -7     # GVS_ERR_INTEGRITY
 
 # gvs_dump_raw / gvs_store_raw regions
@@ -167,7 +171,8 @@ def make_oram_config(capacity, max_batch=4096, device=0, secret_key=None, auth_s
 
 def make_config(msg_capacity, mailbox_partitions=None, mailbox_partition_slots=256,
                 max_batch=None, device=0, secret_key=None, shard_count=0, shard_index=0,
-                route_capacity=0, rows_per_partition=0, auth_storage=False, expiry_per_batch=0):
+                route_capacity=0, rows_per_partition=0, auth_storage=False, expiry_per_batch=0,
+                ed25519_auth=False):
     """Config mirroring gvs_config_init's defaults (R = N/16 mailboxes per shard)."""
     cfg = GvsConfig()
     cfg.shard_count = shard_count
@@ -175,7 +180,7 @@ def make_config(msg_capacity, mailbox_partitions=None, mailbox_partition_slots=2
     cfg.route_capacity = route_capacity
     cfg.expiry_per_batch = expiry_per_batch
     cfg.rows_per_partition = rows_per_partition
-    cfg.flags = FLAG_AUTH_STORAGE if auth_storage else 0
+    cfg.flags = (FLAG_AUTH_STORAGE if auth_storage else 0) | (FLAG_ED25519_AUTH if ed25519_auth else 0)
     cfg.msg_capacity = msg_capacity
     if mailbox_partitions is None:
         r = max(msg_capacity // 16, 256)

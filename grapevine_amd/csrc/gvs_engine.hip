@@ -31,6 +31,7 @@
 #include "gvs_omap.h"
 #include "gvs_wire.h"
 #include "gvs_sr25519.h"
+#include "gvs_ed25519.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
 #ifndef GVS_MA_EXTRA_LDS
@@ -269,6 +270,7 @@ struct gvs_handle {
   int n_marks = 0;
   bool timed = false;
   bool auth = false;         // GVS_FLAG_AUTH_STORAGE
+  bool ed_auth = false;      // GVS_FLAG_ED25519_AUTH: the wire path checks Ed25519 signatures
   bool poisoned = false;     // an integrity failure was seen
   SealCtx sc{};              // storage keys (epoch filled per engine)
   uint32_t* te = nullptr;    // AES table on the device
@@ -280,7 +282,7 @@ struct gvs_handle {
   WireStage wire;
   WirePipe wpipe;
   Bounce bounce;
-  uint8_t* sr_dev = nullptr;  // gvs_sr25519_verify's device staging (grow-only)
+  uint8_t* sr_dev = nullptr;  // gvs_sr25519_verify's / gvs_ed25519_verify's device staging (grow-only)
   size_t sr_cap = 0;
   uint32_t* err_pin = nullptr;  // finish(): the error word's pinned landing place
   std::vector<void*> allocs;
@@ -339,7 +341,7 @@ static int validate(const gvs_config* c) {
     return GVS_ERR_INVALID_ARG;
   if (!is_pow2(c->max_batch) || c->max_batch < 1024 || c->max_batch > (1u << (kSeqBits - 1)))
     return GVS_ERR_INVALID_ARG;
-  if (c->flags & ~GVS_FLAG_AUTH_STORAGE) return GVS_ERR_INVALID_ARG;
+  if (c->flags & ~(GVS_FLAG_AUTH_STORAGE | GVS_FLAG_ED25519_AUTH)) return GVS_ERR_INVALID_ARG;
   // sealed mailbox partitions: the per-row values of k_m1a / k_m2a live in the
   // AES window's holes (gvs_mauth.h)
   if ((c->flags & GVS_FLAG_AUTH_STORAGE) && c->mailbox_partition_slots > kSrAuth) return GVS_ERR_INVALID_ARG;
@@ -720,6 +722,7 @@ static int create_common(const gvs_config* cfg, Mode mode, const uint8_t* comm_i
   h->mode = mode;
   h->device = (int)cfg->device;
   h->auth = (cfg->flags & GVS_FLAG_AUTH_STORAGE) != 0;
+  h->ed_auth = (cfg->flags & GVS_FLAG_ED25519_AUTH) != 0;
   h->S = cfg->shard_count ? cfg->shard_count : 1;
   h->Bsub = cfg->max_batch;
   if (mode == kRccl && cfg->shard_index >= h->S) {
@@ -2129,6 +2132,12 @@ static void enqueue_sr_verify(gvs_handle* h, const sr::SrArgs& a) {
                      dim3(sr::kSrThreads), 0, h->stream, a);
 }
 
+static void enqueue_ed_verify(gvs_handle* h, const sr::EdArgs& a) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(sr::k_ed_verify, dim3((a.n + sr::kSrThreads - 1) / sr::kSrThreads),
+                     dim3(sr::kSrThreads), 0, h->stream, a);
+}
+
 // Handle-owned wire staging: signatures and statuses always (the device path
 // may not pass them), the host-side slabs only for gvs_process_wire_batch.
 static int wire_stage_init(gvs_handle* h, bool io) {
@@ -2162,7 +2171,21 @@ static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const
   uint32_t* status = d_status ? d_status : h->wire.status;
   enqueue_wire_decode(h, d_in, in_stride, d_in_lens, n, d_times, h->in_stage, sigs, status);
   mark(h, "wire_decode");
-  if (d_chal) {
+  if (d_chal && h->ed_auth) {  // pure Ed25519 over the 32 challenge bytes, no context
+    sr::EdArgs a{};
+    a.pk = (const uint8_t*)h->in_stage + 16;  // gvs_request.auth_identity
+    a.pk_stride = sizeof(gvs_request);
+    a.msg = (const uint8_t*)d_chal;
+    a.msg_stride = 32;
+    a.msg_len = 32;
+    a.sig = (const uint8_t*)sigs;
+    a.sig_stride = 64;
+    a.n = n;
+    a.reqs = h->in_stage;
+    a.status = status;
+    enqueue_ed_verify(h, a);
+    mark(h, "ed_verify");
+  } else if (d_chal) {
     sr::SrArgs a;
     (void)sr_args((const uint8_t*)kChallengeContext, sizeof kChallengeContext - 1, a);
     a.pk = (const uint8_t*)h->in_stage + 16;  // gvs_request.auth_identity
@@ -2427,6 +2450,63 @@ int gvs_sr25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, u
   uint32_t* d_ok = (uint32_t*)(d + ((b_pk + b_msg + b_sig + 3) & ~(size_t)3));
   if (int r = gvs_sr25519_verify_device(h, d, 32, d + b_pk, msg_len ? msg_len : 1, msg_len,
                                         d + b_pk + b_msg, 64, n, context, context_len, d_ok))
+    return bounce_done(h, r);
+  if (int r = d2h(h, 4, ok, d_ok, b_ok)) return r;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return bounce_done(h, GVS_OK);
+}
+
+int gvs_ed25519_verify_device(gvs_handle* h, const void* d_pks, uint32_t pk_stride,
+                              const void* d_msgs, uint32_t msg_stride, uint32_t msg_len,
+                              const void* d_sigs, uint32_t sig_stride, uint32_t n, uint32_t* d_ok) {
+  if (!h || pk_stride < 32 || sig_stride < 64 || msg_stride < msg_len || msg_len > 4096 ||
+      (n && (!d_pks || (msg_len && !d_msgs) || !d_sigs || !d_ok)))
+    return GVS_ERR_INVALID_ARG;
+  GVS_HIP(h, hipSetDevice(h->device));
+  sr::EdArgs a{};
+  a.pk = (const uint8_t*)d_pks;
+  a.pk_stride = pk_stride;
+  a.msg = (const uint8_t*)d_msgs;
+  a.msg_stride = msg_stride;
+  a.msg_len = msg_len;
+  a.sig = (const uint8_t*)d_sigs;
+  a.sig_stride = sig_stride;
+  a.n = n;
+  a.ok = d_ok;
+  h->n_marks = 0;
+  mark(h, "start");
+  enqueue_ed_verify(h, a);
+  mark(h, "ed_verify");
+  GVS_HIP(h, hipGetLastError());
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return GVS_OK;
+}
+
+int gvs_ed25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, uint32_t msg_len,
+                       const uint8_t* sigs, uint32_t n, uint32_t* ok) {
+  if (!h || (n && (!pks || (msg_len && !msgs) || !sigs || !ok)) || msg_len > 4096)
+    return GVS_ERR_INVALID_ARG;
+  if (!n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const size_t b_pk = (size_t)n * 32, b_msg = (size_t)n * msg_len, b_sig = (size_t)n * 64,
+               b_ok = (size_t)n * 4;
+  const size_t need = b_pk + b_msg + b_sig + b_ok + 64;
+  // the grow-only device staging of gvs_sr25519_verify
+  if (h->sr_cap < need) {
+    if (h->sr_dev) GVS_HIP(h, hipFree(h->sr_dev));
+    h->sr_dev = nullptr;
+    h->sr_cap = 0;
+    GVS_HIP(h, hipMalloc((void**)&h->sr_dev, need));
+    h->sr_cap = need;
+  }
+  uint8_t* d = h->sr_dev;
+  if (int r = bounce_begin(h)) return r;
+  if (int r = h2d(h, 0, d, pks, b_pk)) return r;
+  if (int r = h2d(h, 1, d + b_pk, msgs, b_msg)) return r;
+  if (int r = h2d(h, 2, d + b_pk + b_msg, sigs, b_sig)) return r;
+  uint32_t* d_ok = (uint32_t*)(d + ((b_pk + b_msg + b_sig + 3) & ~(size_t)3));
+  if (int r = gvs_ed25519_verify_device(h, d, 32, d + b_pk, msg_len ? msg_len : 1, msg_len,
+                                        d + b_pk + b_msg, 64, n, d_ok))
     return bounce_done(h, r);
   if (int r = d2h(h, 4, ok, d_ok, b_ok)) return r;
   GVS_HIP(h, hipStreamSynchronize(h->stream));

@@ -27,6 +27,13 @@ UNAUTHENTICATED.  A batch that overflows a fixed bound (nothing applied)
 fails its callers with RESOURCE_EXHAUSTED; any other store failure (integrity,
 device, exhausted epochs: the handle is dead) fails them with UNAVAILABLE and
 stops the server (`fatal` holds the reason).
+
+Ed25519 clients: serve from an ObliviousStore created with
+`abi.make_config(..., ed25519_auth=True)` (GVS_FLAG_ED25519_AUTH) and give
+each GrapevineClient a `grapevine_amd.ed25519.Ed25519Signer`.  The device then
+checks every auth_signature as a pure Ed25519 signature by auth_identity over
+the 32 challenge bytes (RFC 8032, no context [D]); nothing in this module
+changes, since the store owns the check and the signer protocol is the same.
 """
 import concurrent.futures
 import os

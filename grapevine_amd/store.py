@@ -34,6 +34,7 @@ EXPORTED = (
     "gvs_process_wire_batch", "gvs_process_wire_batch_device", "gvs_wire_decode_device",
     "gvs_wire_encode_device", "gvs_sr25519_verify", "gvs_sr25519_verify_device",
     "gvs_host_alloc", "gvs_host_free", "gvs_process_wire_batches",
+    "gvs_ed25519_verify", "gvs_ed25519_verify_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -78,7 +79,9 @@ def load_library(path=None):
     lib.gvs_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
     lib.gvs_host_free.argtypes = [vp, vp]
     lib.gvs_sr25519_verify_device.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, u32, vp, u32, vp]
-    lib.gvs_wire_decode_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, vp]
+    lib.gvs_ed25519_verify.argtypes = [vp, vp, vp, u32, vp, u32, vp]
+    lib.gvs_ed25519_verify_device.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, u32, vp]
+    lib.gvs_wire_decode_device.argtypes =[vp, vp, u32, vp, u32, vp, vp, vp, vp]
     lib.gvs_wire_encode_device.argtypes = [vp, vp, u32, vp, u32, vp]
     lib.gvs_process_batches.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(u32)]
     lib.gvs_access.argtypes = [vp, vp, vp]
@@ -342,6 +345,20 @@ class ObliviousStore:
                                                 msgs.shape[1] if msgs.ndim == 2 else 0,
                                                 sigs.ctypes.data, n, context, len(context),
                                                 ok.ctypes.data))
+        return ok.astype(bool)
+
+    def ed25519_verify(self, pks, msgs, sigs):
+        """Batched Ed25519 verification on the device (gvs_ed25519_verify; RFC
+        8032 strict decoding, cofactorless): pks (n, 32), msgs (n, L), sigs
+        (n, 64) uint8 -> (n,) bool."""
+        pks = np.ascontiguousarray(pks, np.uint8)
+        msgs = np.ascontiguousarray(msgs, np.uint8)
+        sigs = np.ascontiguousarray(sigs, np.uint8)
+        n = len(pks)
+        ok = np.zeros(n, np.uint32)
+        self._check(self.lib.gvs_ed25519_verify(self.h, pks.ctypes.data, msgs.ctypes.data,
+                                                msgs.shape[1] if msgs.ndim == 2 else 0,
+                                                sigs.ctypes.data, n, ok.ctypes.data))
         return ok.astype(bool)
 
     def access(self, req):

@@ -91,6 +91,9 @@ extern "C" {
 
 /* gvs_config.flags */
 #define GVS_FLAG_AUTH_STORAGE 1u /* AES-CTR sealed tables, a MAC per row */
+#define GVS_FLAG_ED25519_AUTH 2u /* the wire path checks challenge signatures as Ed25519
+                                    instead of schnorrkel (gvs_create, gvs_create_sharded
+                                    only; alone or with GVS_FLAG_AUTH_STORAGE) */
 
 /* ---- records ------------------------------------------------------------- */
 
@@ -274,8 +277,12 @@ int gvs_process_batches_device(gvs_handle *h, const void *d_reqs, const uint32_t
  * challenge each request's auth_signature must sign (README.md:187-200); a
  * request whose signature does not verify as a schnorrkel signature by its
  * auth_identity under the context "grapevine-challenge" (types/src/lib.rs:13)
- * becomes a hard error (decode_status GVS_WIRE_BAD_SIGNATURE).  NULL: no
- * check (the caller verified).  sigs (optional) receives each request's 64-B
+ * becomes a hard error (decode_status GVS_WIRE_BAD_SIGNATURE).  On a handle
+ * created with GVS_FLAG_ED25519_AUTH the check is gvs_ed25519_verify's
+ * instead: auth_identity is an Ed25519 public key and the signed message is
+ * the 32 challenge bytes, pure Ed25519 with no context [D: the reference
+ * README says the service could be compiled to use ed25519, not what that
+ * build would sign].  NULL: no check (the caller verified).  sigs (optional) receives each request's 64-B
  * auth_signature (zero when it failed to decode); decode_status (optional)
  * one GVS_WIRE_* per request. */
 int gvs_process_wire_batch(gvs_handle *h, const uint8_t *in, uint32_t in_stride,
@@ -327,6 +334,20 @@ int gvs_sr25519_verify_device(gvs_handle *h, const void *d_pks, uint32_t pk_stri
                               const void *d_msgs, uint32_t msg_stride, uint32_t msg_len,
                               const void *d_sigs, uint32_t sig_stride, uint32_t n,
                               const uint8_t *context, uint32_t context_len, uint32_t *d_ok);
+
+/* Ed25519 signature check (RFC 8032 §5.1.7): ok[k] = 1 iff sigs[k] (R || s,
+ * 64 B) is a valid pure-Ed25519 signature by the public key pks[k] on msgs[k]
+ * (msg_len bytes, at most 4096), else 0.  The rule [D]: strict decoding of
+ * the key and of R (y < p, x on the curve, not x = 0 with the sign bit), s < l,
+ * the cofactorless equation s*B = R + h*A, no small-order test; not
+ * ed25519-dalek's legacy acceptance rules.  Batched on the handle's device
+ * like gvs_sr25519_verify, one thread per signature, the same instruction
+ * stream whatever the inputs; the device form takes the same strides. */
+int gvs_ed25519_verify(gvs_handle *h, const uint8_t *pks, const uint8_t *msgs, uint32_t msg_len,
+                       const uint8_t *sigs, uint32_t n, uint32_t *ok);
+int gvs_ed25519_verify_device(gvs_handle *h, const void *d_pks, uint32_t pk_stride,
+                              const void *d_msgs, uint32_t msg_stride, uint32_t msg_len,
+                              const void *d_sigs, uint32_t sig_stride, uint32_t n, uint32_t *d_ok);
 
 /* Message expiry (README.md:86-99: the untrusted host supplies the time and
  * the expiry period).  From the next batch on, messages whose timestamp is
