@@ -13,8 +13,9 @@ HDRS := $(wildcard grapevine_amd/csrc/*.h) include/gvstore.h include/gvstore_tes
 
 SRHOST := tests/libsrhost.so
 EDHOST := tests/libedhost.so
+CHACHAHOST := tests/libchachahost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -31,11 +32,16 @@ $(SRHOST): tests/sr_host.cpp grapevine_amd/csrc/gvs_sr25519.h grapevine_amd/csrc
 $(EDHOST): tests/ed_host.cpp grapevine_amd/csrc/gvs_ed25519.h grapevine_amd/csrc/gvs_sr25519.h grapevine_amd/csrc/gvs_device.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/ed_host.cpp
 
+# the device challenge stream (ChaCha20 block, draw selection) built for the
+# CPU (tests/test_chacha_host.py)
+$(CHACHAHOST): tests/chacha_host.cpp grapevine_amd/csrc/gvs_chacha.h
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/chacha_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -32,6 +32,7 @@
 #include "gvs_wire.h"
 #include "gvs_sr25519.h"
 #include "gvs_ed25519.h"
+#include "gvs_chacha.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
 #ifndef GVS_MA_EXTRA_LDS
@@ -210,7 +211,9 @@ struct WireStage {
   uint64_t* times = nullptr;
   uint4* sigs = nullptr;
   uint32_t* status = nullptr;
-  uint4* chal = nullptr;     // n x 32-B challenges
+  uint4* chal = nullptr;     // n x 32-B challenges (given, or derived from seeds and draws)
+  uint4* seeds = nullptr;    // seeded calls: n x 32-B channel seeds
+  uint64_t* draws = nullptr; // seeded calls: n draw indices
 };
 
 // Double-buffered wire path (gvs_process_wire_batches): per slot, the device
@@ -226,6 +229,14 @@ struct WirePipe {
   uint32_t *hlens[2] = {}, *holens[2] = {}, *hstat[2] = {};
   uint64_t* htimes[2] = {};
   hipEvent_t h2d[2] = {}, done[2] = {}, d2h[2] = {};
+  // seeded calls (gvs_process_wire_batches_seeded), allocated on their first
+  // use: seeds and draw indices go up where the challenges would, and the
+  // challenges derived into dchal[b] come down with the results
+  bool seeded = false;
+  uint4* dseed[2] = {};
+  uint64_t* ddraw[2] = {};
+  uint8_t *hseed[2] = {}, *hchout[2] = {};
+  uint64_t* hdraw[2] = {};
 };
 
 // Pinned bounce buffers of the single-call host APIs (gvs_process_batch, the
@@ -237,7 +248,7 @@ struct WirePipe {
 // (DESIGN.md §3 "Counters").  Pageable caller memory is therefore copied by
 // the host into grow-only pinned buffers and moved by DMA from there.
 struct Bounce {
-  static constexpr int kSlots = 8;  // 0..3 in, 4..7 out
+  static constexpr int kSlots = 10;  // 0..3 and 8 in, 4..7 and 9 out
   void* buf[kSlots] = {};
   size_t cap[kSlots] = {};
   struct Out {
@@ -1707,7 +1718,8 @@ int gvs_destroy(gvs_handle* h) {
   WirePipe& wp = h->wpipe;
   for (int b = 0; b < 2; ++b) {
     for (void* q : {(void*)wp.hin[b], (void*)wp.hout[b], (void*)wp.hchal[b], (void*)wp.hlens[b],
-                    (void*)wp.holens[b], (void*)wp.hstat[b], (void*)wp.htimes[b]})
+                    (void*)wp.holens[b], (void*)wp.hstat[b], (void*)wp.htimes[b], (void*)wp.hseed[b],
+                    (void*)wp.hchout[b], (void*)wp.hdraw[b]})
       if (q) (void)hipHostFree(q);
     for (hipEvent_t ev : {wp.h2d[b], wp.done[b], wp.d2h[b]})
       if (ev) (void)hipEventDestroy(ev);
@@ -1815,7 +1827,7 @@ static int bounce_grow(gvs_handle* h, int slot, size_t bytes) {
 }
 
 // host -> device from caller memory `src`: pinned memory is copied from
-// directly, pageable memory through bounce slot `slot` (0..3)
+// directly, pageable memory through bounce slot `slot` (0..3, 8)
 static int h2d(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes) {
   if (!bytes) return GVS_OK;
   if (!is_pinned(src)) {
@@ -1829,7 +1841,7 @@ static int h2d(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes
 }
 
 // device -> host into caller memory `dst`: pageable memory through bounce
-// slot `slot` (4..7), handed over by bounce_done after the stream's sync
+// slot `slot` (4..7, 9), handed over by bounce_done after the stream's sync
 static int d2h(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes) {
   if (!bytes) return GVS_OK;
   if (is_pinned(dst)) {
@@ -2138,9 +2150,19 @@ static void enqueue_ed_verify(gvs_handle* h, const sr::EdArgs& a) {
                      dim3(sr::kSrThreads), 0, h->stream, a);
 }
 
+static void enqueue_challenge(gvs_handle* h, const void* d_seeds, const uint64_t* d_draws, uint32_t n,
+                              void* d_out) {
+  if (!n) return;
+  ChallengeArgs a{(const uint4*)d_seeds, d_draws, (uint4*)d_out, n};
+  hipLaunchKernelGGL(k_challenge, dim3((n + kChallengeThreads - 1) / kChallengeThreads),
+                     dim3(kChallengeThreads), 0, h->stream, a);
+}
+
 // Handle-owned wire staging: signatures and statuses always (the device path
-// may not pass them), the host-side slabs only for gvs_process_wire_batch.
-static int wire_stage_init(gvs_handle* h, bool io) {
+// may not pass them), the host-side slabs only for gvs_process_wire_batch, the
+// seeds and draw indices only for the seeded host call (the seeded device call
+// needs the challenge staging alone).
+static int wire_stage_init(gvs_handle* h, bool io, bool seeded = false) {
   WireStage& w = h->wire;
   const uint64_t cap = max_submit(h);
   if (!w.sigs) {
@@ -2153,20 +2175,39 @@ static int wire_stage_init(gvs_handle* h, bool io) {
     if (int rc = dalloc_t(h, &w.in_lens, cap)) return rc;
     if (int rc = dalloc_t(h, &w.out_lens, cap)) return rc;
     if (int rc = dalloc_t(h, &w.times, cap)) return rc;
+  }
+  if ((io || seeded) && !w.chal)
     if (int rc = dalloc_t(h, &w.chal, cap * 2)) return rc;
+  if (io && seeded && !w.seeds) {
+    if (int rc = dalloc_t(h, &w.seeds, cap * 2)) return rc;
+    if (int rc = dalloc_t(h, &w.draws, cap)) return rc;
   }
   return GVS_OK;
 }
 
+// Where a wire batch's challenges come from: `chal` as given (n x 32 B), or,
+// with `seeds` (n x 32 B) and `draws` (n u64), derived by k_challenge into
+// `chal`, a staging buffer.  All null: signatures are not checked.
+struct ChalSrc {
+  void* chal = nullptr;
+  const void* seeds = nullptr;
+  const uint64_t* draws = nullptr;
+};
+
 // decode -> (challenge check) -> the batch -> encode, all on the engine
 // stream; the request and response slabs live in the handle's host-API
-// staging.  d_chal: n x 32-B challenges, or null (signatures not checked).
+// staging.
 static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const uint32_t* d_in_lens,
-                      uint32_t n, const uint64_t* d_times, const void* d_chal, void* d_out,
+                      uint32_t n, const uint64_t* d_times, const ChalSrc& cs, void* d_out,
                       uint32_t out_stride, uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status) {
   if (int rc = wire_stage_init(h, false)) return rc;
   h->n_marks = 0;
   mark(h, "start");
+  const void* d_chal = cs.chal;
+  if (cs.seeds) {
+    enqueue_challenge(h, cs.seeds, cs.draws, n, cs.chal);
+    mark(h, "challenge");
+  }
   uint4* sigs = d_sigs ? (uint4*)d_sigs : h->wire.sigs;
   uint32_t* status = d_status ? d_status : h->wire.status;
   enqueue_wire_decode(h, d_in, in_stride, d_in_lens, n, d_times, h->in_stage, sigs, status);
@@ -2208,46 +2249,102 @@ static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const
   return GVS_OK;
 }
 
+// The callers' challenge arguments, as the explicit calls (challenges) or the
+// seeded calls (seeds + draws, and where to return what was derived) pass
+// them.  A seeded call passes both seeds and draws, or neither.
+struct ChalIn {
+  const void* challenges = nullptr;
+  const void* seeds = nullptr;
+  const uint64_t* draws = nullptr;
+  void* challenges_out = nullptr;
+  bool ok() const { return !seeds == !draws; }
+  bool seeded() const { return seeds != nullptr; }
+};
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// gvs_process_wire_batch_device and its seeded form
+static int wire_batch_device(gvs_handle* h, const void* d_in, uint32_t in_stride,
+                             const uint32_t* d_in_lens, uint32_t n, const uint64_t* d_times,
+                             const ChalIn& ci, void* d_out, uint32_t out_stride,
+                             uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status) {
+  if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) || n > max_submit(h) ||
+      (n && (!d_in || !d_in_lens || !d_times || !d_out || !d_out_lens)) || !ci.ok() ||
+      !aligned16(ci.seeds) || !aligned16(ci.challenges_out))
+    return GVS_ERR_INVALID_ARG;
+  if (h->poisoned) return GVS_ERR_INTEGRITY;
+  if (int r = check_epoch(h)) return r;
+  GVS_HIP(h, hipSetDevice(h->device));
+  ChalSrc cs{const_cast<void*>(ci.challenges), nullptr, nullptr};
+  if (ci.seeded()) {
+    if (int rc = wire_stage_init(h, false, true)) return rc;
+    cs = ChalSrc{h->wire.chal, ci.seeds, ci.draws};
+  }
+  if (int r = reset_errors(h)) return r;
+  if (int r = wire_batch(h, d_in, in_stride, d_in_lens, n, d_times, cs, d_out, out_stride,
+                         d_out_lens, d_sigs, d_status))
+    return r;
+  if (n && ci.seeded() && ci.challenges_out)
+    GVS_HIP(h, hipMemcpyAsync(ci.challenges_out, cs.chal, (size_t)n * 32, hipMemcpyDeviceToDevice,
+                              h->stream));
+  return finish(h);
+}
+
 int gvs_process_wire_batch_device(gvs_handle* h, const void* d_in, uint32_t in_stride,
                                   const uint32_t* d_in_lens, uint32_t n, const uint64_t* d_times,
                                   const void* d_challenges, void* d_out, uint32_t out_stride,
                                   uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status) {
-  if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) || n > max_submit(h) ||
-      (n && (!d_in || !d_in_lens || !d_times || !d_out || !d_out_lens)))
-    return GVS_ERR_INVALID_ARG;
-  if (h->poisoned) return GVS_ERR_INTEGRITY;
-  if (int r = check_epoch(h)) return r;
-  GVS_HIP(h, hipSetDevice(h->device));
-  if (int r = reset_errors(h)) return r;
-  if (int r = wire_batch(h, d_in, in_stride, d_in_lens, n, d_times, d_challenges, d_out,
-                         out_stride, d_out_lens, d_sigs, d_status))
-    return r;
-  return finish(h);
+  ChalIn ci;
+  ci.challenges = d_challenges;
+  return wire_batch_device(h, d_in, in_stride, d_in_lens, n, d_times, ci, d_out, out_stride,
+                           d_out_lens, d_sigs, d_status);
 }
 
-int gvs_process_wire_batch(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
+int gvs_process_wire_batch_seeded_device(gvs_handle* h, const void* d_in, uint32_t in_stride,
+                                         const uint32_t* d_in_lens, uint32_t n,
+                                         const uint64_t* d_times, const void* d_seeds,
+                                         const uint64_t* d_draws, void* d_out, uint32_t out_stride,
+                                         uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status,
+                                         void* d_challenges_out) {
+  ChalIn ci;
+  ci.seeds = d_seeds;
+  ci.draws = d_draws;
+  ci.challenges_out = d_challenges_out;
+  return wire_batch_device(h, d_in, in_stride, d_in_lens, n, d_times, ci, d_out, out_stride,
+                           d_out_lens, d_sigs, d_status);
+}
+
+// gvs_process_wire_batch and its seeded form
+static int wire_batch_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
                            const uint32_t* in_lens, uint32_t n, const uint64_t* times,
-                           const uint8_t* challenges, uint8_t* out, uint32_t out_stride,
-                           uint32_t* out_lens, uint8_t* sigs, uint32_t* decode_status) {
+                           const ChalIn& ci, uint8_t* out, uint32_t out_stride, uint32_t* out_lens,
+                           uint8_t* sigs, uint32_t* decode_status) {
   if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) || n > max_submit(h) ||
-      (n && (!in || !in_lens || !times || !out || !out_lens)))
+      (n && (!in || !in_lens || !times || !out || !out_lens)) || !ci.ok())
     return GVS_ERR_INVALID_ARG;
   if (h->poisoned) return GVS_ERR_INTEGRITY;
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
-  if (int rc = wire_stage_init(h, true)) return rc;
+  if (int rc = wire_stage_init(h, true, ci.seeded())) return rc;
   WireStage& w = h->wire;
   if (int r = bounce_begin(h)) return r;
   if (n) {
     if (int r = h2d(h, 0, w.in, in, (size_t)n * in_stride)) return r;
     if (int r = h2d(h, 1, w.in_lens, in_lens, (size_t)n * 4)) return r;
     if (int r = h2d(h, 2, w.times, times, (size_t)n * 8)) return r;
-    if (challenges)
-      if (int r = h2d(h, 3, w.chal, challenges, (size_t)n * 32)) return r;
+    if (ci.challenges)
+      if (int r = h2d(h, 3, w.chal, ci.challenges, (size_t)n * 32)) return r;
+    if (ci.seeded()) {
+      if (int r = h2d(h, 3, w.seeds, ci.seeds, (size_t)n * 32)) return r;
+      if (int r = h2d(h, 8, w.draws, ci.draws, (size_t)n * 8)) return r;
+    }
   }
+  ChalSrc cs;
+  if (ci.challenges) cs.chal = w.chal;
+  if (ci.seeded()) cs = ChalSrc{w.chal, w.seeds, w.draws};
   if (int r = reset_errors(h)) return r;
-  if (int r = wire_batch(h, w.in, in_stride, w.in_lens, n, w.times, challenges ? w.chal : nullptr,
-                         w.out, out_stride, w.out_lens, w.sigs, w.status))
+  if (int r = wire_batch(h, w.in, in_stride, w.in_lens, n, w.times, cs, w.out, out_stride,
+                         w.out_lens, w.sigs, w.status))
     return r;
   if (n) {
     if (int r = d2h(h, 4, out, w.out, (size_t)n * out_stride)) return r;
@@ -2256,8 +2353,48 @@ int gvs_process_wire_batch(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
       if (int r = d2h(h, 6, sigs, w.sigs, (size_t)n * 64)) return r;
     if (decode_status)
       if (int r = d2h(h, 7, decode_status, w.status, (size_t)n * 4)) return r;
+    if (ci.seeded() && ci.challenges_out)
+      if (int r = d2h(h, 9, ci.challenges_out, w.chal, (size_t)n * 32)) return r;
   }
   return bounce_done(h, finish(h));
+}
+
+int gvs_process_wire_batch(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
+                           const uint32_t* in_lens, uint32_t n, const uint64_t* times,
+                           const uint8_t* challenges, uint8_t* out, uint32_t out_stride,
+                           uint32_t* out_lens, uint8_t* sigs, uint32_t* decode_status) {
+  ChalIn ci;
+  ci.challenges = challenges;
+  return wire_batch_host(h, in, in_stride, in_lens, n, times, ci, out, out_stride, out_lens, sigs,
+                         decode_status);
+}
+
+int gvs_process_wire_batch_seeded(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
+                                  const uint32_t* in_lens, uint32_t n, const uint64_t* times,
+                                  const uint8_t* seeds, const uint64_t* draws, uint8_t* out,
+                                  uint32_t out_stride, uint32_t* out_lens, uint8_t* sigs,
+                                  uint32_t* decode_status, uint8_t* challenges_out) {
+  ChalIn ci;
+  ci.seeds = seeds;
+  ci.draws = draws;
+  ci.challenges_out = challenges_out;
+  return wire_batch_host(h, in, in_stride, in_lens, n, times, ci, out, out_stride, out_lens, sigs,
+                         decode_status);
+}
+
+static int wire_pipe_seeded_init(gvs_handle* h) {
+  WirePipe& p = h->wpipe;
+  if (p.seeded) return GVS_OK;
+  const uint64_t cap = max_submit(h);
+  for (int b = 0; b < 2; ++b) {
+    if (int rc = dalloc_t(h, &p.dseed[b], cap * 2)) return rc;
+    if (int rc = dalloc_t(h, &p.ddraw[b], cap)) return rc;
+    GVS_HIP(h, hipHostMalloc((void**)&p.hseed[b], cap * 32, hipHostMallocDefault));
+    GVS_HIP(h, hipHostMalloc((void**)&p.hdraw[b], cap * 8, hipHostMallocDefault));
+    GVS_HIP(h, hipHostMalloc((void**)&p.hchout[b], cap * 32, hipHostMallocDefault));
+  }
+  p.seeded = true;
+  return GVS_OK;
 }
 
 static int wire_pipe_init(gvs_handle* h) {
@@ -2292,22 +2429,28 @@ static int wire_pipe_init(gvs_handle* h) {
 // batch t+1's messages go up on the copy stream and batch t-1's results come
 // down on the other while batch t runs (decode, challenge check, the store,
 // encode).  At the first batch that fails, its error is returned and it and
-// the later batches are not applied.
-int gvs_process_wire_batches(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
+// the later batches are not applied.  (gvs_process_wire_batches and its seeded
+// form.)
+static int wire_batches_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
                              const uint32_t* in_lens, const uint32_t* counts, uint32_t k,
-                             const uint64_t* times, const uint8_t* challenges, uint8_t* out,
+                             const uint64_t* times, const ChalIn& ci, uint8_t* out,
                              uint32_t out_stride, uint32_t* out_lens, uint32_t* decode_status,
                              uint32_t* applied) {
   if (applied) *applied = 0;
   if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) ||
-      (k && (!counts || !in || !in_lens || !times || !out || !out_lens)))
+      (k && (!counts || !in || !in_lens || !times || !out || !out_lens)) || !ci.ok())
     return GVS_ERR_INVALID_ARG;
+  const uint8_t* challenges = (const uint8_t*)ci.challenges;
+  const uint8_t* seeds = (const uint8_t*)ci.seeds;
+  uint8_t* chal_out = ci.seeded() ? (uint8_t*)ci.challenges_out : nullptr;
   for (uint32_t t = 0; t < k; ++t)
     if (counts[t] > max_submit(h)) return GVS_ERR_INVALID_ARG;
   if (h->poisoned) return GVS_ERR_INTEGRITY;
   if (k == 0) return GVS_OK;
   GVS_HIP(h, hipSetDevice(h->device));
   if (int r = wire_pipe_init(h)) return r;
+  if (seeds)
+    if (int r = wire_pipe_seeded_init(h)) return r;
   if (int r = wire_stage_init(h, false)) return r;
   WirePipe& p = h->wpipe;
   HostPipe& hp = h->pipe;
@@ -2335,6 +2478,10 @@ int gvs_process_wire_batches(gvs_handle* h, const uint8_t* in, uint32_t in_strid
       std::memcpy(p.hlens[b], in_lens + next_off, (size_t)n * 4);
       std::memcpy(p.htimes[b], times + next_off, (size_t)n * 8);
       if (challenges) std::memcpy(p.hchal[b], challenges + next_off * 32, (size_t)n * 32);
+      if (seeds) {
+        std::memcpy(p.hseed[b], seeds + next_off * 32, (size_t)n * 32);
+        std::memcpy(p.hdraw[b], ci.draws + next_off, (size_t)n * 8);
+      }
       if (t >= 2) GVS_HIP(h, hipStreamWaitEvent(hp.copy, p.done[b], 0));  // device slot b consumed
       if (n) {
         GVS_HIP(h, hipMemcpyAsync(p.din[b], src, (size_t)n * in_stride, hipMemcpyHostToDevice, hp.copy));
@@ -2342,14 +2489,20 @@ int gvs_process_wire_batches(gvs_handle* h, const uint8_t* in, uint32_t in_strid
         GVS_HIP(h, hipMemcpyAsync(p.dtimes[b], p.htimes[b], (size_t)n * 8, hipMemcpyHostToDevice, hp.copy));
         if (challenges)
           GVS_HIP(h, hipMemcpyAsync(p.dchal[b], p.hchal[b], (size_t)n * 32, hipMemcpyHostToDevice, hp.copy));
+        if (seeds) {
+          GVS_HIP(h, hipMemcpyAsync(p.dseed[b], p.hseed[b], (size_t)n * 32, hipMemcpyHostToDevice, hp.copy));
+          GVS_HIP(h, hipMemcpyAsync(p.ddraw[b], p.hdraw[b], (size_t)n * 8, hipMemcpyHostToDevice, hp.copy));
+        }
       }
       GVS_HIP(h, hipEventRecord(p.h2d[b], hp.copy));
       GVS_HIP(h, hipStreamWaitEvent(s, p.h2d[b], 0));
       if (t >= 2) GVS_HIP(h, hipStreamWaitEvent(s, p.d2h[b], 0));  // results b copied out
       snap[b] = save_state(h);
-      if (int r = wire_batch(h, p.din[b], in_stride, p.dlens[b], n, p.dtimes[b],
-                             challenges ? p.dchal[b] : nullptr, p.dout[b], out_stride, p.dolens[b],
-                             nullptr, p.dstat[b]))
+      ChalSrc cs;
+      if (challenges) cs.chal = p.dchal[b];
+      if (seeds) cs = ChalSrc{p.dchal[b], p.dseed[b], p.ddraw[b]};
+      if (int r = wire_batch(h, p.din[b], in_stride, p.dlens[b], n, p.dtimes[b], cs, p.dout[b],
+                             out_stride, p.dolens[b], nullptr, p.dstat[b]))
         return r;
       if (h->mode != kSingle)
         if (int r = agree_errors(h)) return r;
@@ -2362,6 +2515,8 @@ int gvs_process_wire_batches(gvs_handle* h, const uint8_t* in, uint32_t in_strid
                                   (size_t)n * out_stride, hipMemcpyDeviceToHost, hp.copy_out));
         GVS_HIP(h, hipMemcpyAsync(p.holens[b], p.dolens[b], (size_t)n * 4, hipMemcpyDeviceToHost, hp.copy_out));
         GVS_HIP(h, hipMemcpyAsync(p.hstat[b], p.dstat[b], (size_t)n * 4, hipMemcpyDeviceToHost, hp.copy_out));
+        if (chal_out)
+          GVS_HIP(h, hipMemcpyAsync(p.hchout[b], p.dchal[b], (size_t)n * 32, hipMemcpyDeviceToHost, hp.copy_out));
       }
       GVS_HIP(h, hipEventRecord(p.d2h[b], hp.copy_out));
       advance(h);  // as if applied; rolled back below if it was not
@@ -2384,16 +2539,85 @@ int gvs_process_wire_batches(gvs_handle* h, const uint8_t* in, uint32_t in_strid
         std::memset(out + off[pb] * out_stride, 0, (size_t)(total - off[pb]) * out_stride);
         std::memset(out_lens + off[pb], 0, (size_t)(total - off[pb]) * 4);
         if (decode_status) std::memset(decode_status + off[pb], 0, (size_t)(total - off[pb]) * 4);
+        if (chal_out) std::memset(chal_out + off[pb] * 32, 0, (size_t)(total - off[pb]) * 32);
         return decode_error(h, e);
       }
       if (!pin_out) par_memcpy(out + off[pb] * out_stride, p.hout[pb], (size_t)n * out_stride);
       std::memcpy(out_lens + off[pb], p.holens[pb], (size_t)n * 4);
       if (decode_status) std::memcpy(decode_status + off[pb], p.hstat[pb], (size_t)n * 4);
+      if (chal_out) std::memcpy(chal_out + off[pb] * 32, p.hchout[pb], (size_t)n * 32);
       if (applied) *applied = t;
     }
     if (!more && t >= enq) break;
   }
   return stop;
+}
+
+int gvs_process_wire_batches(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
+                             const uint32_t* in_lens, const uint32_t* counts, uint32_t k,
+                             const uint64_t* times, const uint8_t* challenges, uint8_t* out,
+                             uint32_t out_stride, uint32_t* out_lens, uint32_t* decode_status,
+                             uint32_t* applied) {
+  ChalIn ci;
+  ci.challenges = challenges;
+  return wire_batches_host(h, in, in_stride, in_lens, counts, k, times, ci, out, out_stride,
+                           out_lens, decode_status, applied);
+}
+
+int gvs_process_wire_batches_seeded(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
+                                    const uint32_t* in_lens, const uint32_t* counts, uint32_t k,
+                                    const uint64_t* times, const uint8_t* seeds,
+                                    const uint64_t* draws, uint8_t* out, uint32_t out_stride,
+                                    uint32_t* out_lens, uint32_t* decode_status,
+                                    uint8_t* challenges_out, uint32_t* applied) {
+  ChalIn ci;
+  ci.seeds = seeds;
+  ci.draws = draws;
+  ci.challenges_out = challenges_out;
+  return wire_batches_host(h, in, in_stride, in_lens, counts, k, times, ci, out, out_stride,
+                           out_lens, decode_status, applied);
+}
+
+// Challenge derivation alone (gvs_chacha.h): out[k] = draw number draws[k] of
+// ChaCha20Rng(seeds[k]).  Synchronous on the handle's stream.
+int gvs_challenge_derive_device(gvs_handle* h, const void* d_seeds, const uint64_t* d_draws,
+                                uint32_t n, void* d_out) {
+  if (!h || (n && (!d_seeds || !d_draws || !d_out)) || !aligned16(d_seeds) || !aligned16(d_out))
+    return GVS_ERR_INVALID_ARG;
+  GVS_HIP(h, hipSetDevice(h->device));
+  h->n_marks = 0;
+  mark(h, "start");
+  enqueue_challenge(h, d_seeds, d_draws, n, d_out);
+  mark(h, "challenge");
+  GVS_HIP(h, hipGetLastError());
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return GVS_OK;
+}
+
+int gvs_challenge_derive(gvs_handle* h, const uint8_t* seeds, const uint64_t* draws, uint32_t n,
+                         uint8_t* out) {
+  if (!h || (n && (!seeds || !draws || !out))) return GVS_ERR_INVALID_ARG;
+  if (!n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const size_t b_seed = (size_t)n * 32, b_draw = (size_t)n * 8;
+  const size_t need = 2 * b_seed + b_draw;
+  // the grow-only device staging of gvs_sr25519_verify
+  if (h->sr_cap < need) {
+    if (h->sr_dev) GVS_HIP(h, hipFree(h->sr_dev));
+    h->sr_dev = nullptr;
+    h->sr_cap = 0;
+    GVS_HIP(h, hipMalloc((void**)&h->sr_dev, need));
+    h->sr_cap = need;
+  }
+  uint8_t* d = h->sr_dev;  // seeds | out | draws: every part 16-byte aligned
+  if (int r = bounce_begin(h)) return r;
+  if (int r = h2d(h, 0, d, seeds, b_seed)) return r;
+  if (int r = h2d(h, 1, d + 2 * b_seed, draws, b_draw)) return r;
+  if (int r = gvs_challenge_derive_device(h, d, (const uint64_t*)(d + 2 * b_seed), n, d + b_seed))
+    return bounce_done(h, r);
+  if (int r = d2h(h, 4, out, d + b_seed, b_seed)) return r;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return bounce_done(h, GVS_OK);
 }
 
 int gvs_sr25519_verify_device(gvs_handle* h, const void* d_pks, uint32_t pk_stride,

@@ -20,6 +20,11 @@ tests/test_server.py).  The attest messages follow mobilecoin's attest.proto
 (absent from the reference; `AuthMessage {bytes data = 1}`, `Message {bytes
 aad = 1; bytes channel_id = 2; bytes data = 3}` [U]).
 
+With `GrapevineServer(device_challenges=True)` the host keeps only the seed
+and a draw counter per channel and the store derives each batch's challenges
+on the device (`gvs_process_wire_batch_seeded`, gvs_chacha.h); the client
+still signs over its own ChallengeRng stream.
+
 Errors: a request the store answers as a hard error (decode failure, wrong
 field sizes, a proto fail-fast rule) fails with INVALID_ARGUMENT; a bad
 challenge signature with UNAUTHENTICATED; an unknown channel with
@@ -99,6 +104,24 @@ class ChallengeRng:
         return out
 
 
+class ChallengeCounter:
+    """A channel whose challenges the device derives (GrapevineServer with
+    device_challenges=True): the seed and the index of the next draw.  `draw`
+    hands out (seed, index) and advances, as ChallengeRng.draw hands out the
+    32 bytes that gvs_challenge_derive computes from that pair."""
+
+    def __init__(self, seed):
+        if len(seed) != 32:
+            raise ValueError("challenge seed must be 32 bytes")
+        self.seed, self.next_draw = bytes(seed), 0
+
+    def draw(self, n=32):
+        if n != 32:
+            raise ValueError("a challenge is one 32-byte draw")
+        d, self.next_draw = self.next_draw, self.next_draw + 1
+        return self.seed, d
+
+
 # --------------------------------------------------------- attest messages [U]
 
 def _ld(field, data):
@@ -176,14 +199,23 @@ class GrapevineServer:
     window_ms: how long the batcher waits after the first request of a batch
     for more; max_batch: the most requests per GPU batch.  on_batch(msgs,
     times, challenges, responses, statuses), if given, sees every batch (tests
-    replay them into the oracle)."""
+    replay them into the oracle).
+
+    device_challenges: the host keeps only (seed, next draw index) per channel
+    and every batch goes through `process_wire_batch_seeded`, which derives
+    the challenges on the device (gvs_chacha.h) and returns them; on_batch
+    sees those in the `challenges` position.  With verify=False nothing is
+    derived (on_batch sees zeros).  False: the host draws every challenge
+    from its own ChallengeRng."""
 
     def __init__(self, store, address="127.0.0.1:0", window_ms=2.0, max_batch=1024,
-                 verify=True, clock=None, on_batch=None, workers=64, call_timeout=60.0):
+                 verify=True, clock=None, on_batch=None, workers=64, call_timeout=60.0,
+                 device_challenges=False):
         import grpc
         self.grpc = grpc
         self.store, self.window, self.max_batch = store, window_ms * 1e-3, max_batch
         self.verify, self.on_batch = verify, on_batch
+        self.device_challenges = device_challenges
         self.clock = clock or (lambda: int(time.time()))
         self.channels, self.lock = {}, threading.Lock()
         self.q = queue.Queue()
@@ -216,7 +248,8 @@ class GrapevineServer:
     def _auth(self, request, context):
         seed, cid = os.urandom(32), os.urandom(16)
         with self.lock:
-            self.channels[cid] = (ChallengeRng(seed), threading.Lock())
+            rng = ChallengeCounter(seed) if self.device_challenges else ChallengeRng(seed)
+            self.channels[cid] = (rng, threading.Lock())
         return encode_auth_reply(cid, seed)
 
     def _query(self, request, context):
@@ -277,12 +310,21 @@ class GrapevineServer:
         msgs = [p.data for p in batch]
         now = self.clock()
         times = np.full(len(batch), now, np.uint64)
-        chal = np.frombuffer(b"".join(p.challenge for p in batch), np.uint8).reshape(-1, 32)
+        if self.device_challenges:  # p.challenge is (seed, draw index)
+            seeds = np.frombuffer(b"".join(p.challenge[0] for p in batch), np.uint8).reshape(-1, 32)
+            draws = np.array([p.challenge[1] for p in batch], np.uint64)
+            chal = np.zeros((len(batch), 32), np.uint8)
+        else:
+            chal = np.frombuffer(b"".join(p.challenge for p in batch), np.uint8).reshape(-1, 32)
         resp, status = [b""] * len(batch), np.full(len(batch), _ST_FATAL, np.uint32)
         try:
             try:
-                resp, _, status = self.store.process_wire_batch(
-                    msgs, times, challenges=chal if self.verify else None)
+                if self.device_challenges:
+                    resp, _, status, chal = self.store.process_wire_batch_seeded(
+                        msgs, times, seeds if self.verify else None, draws if self.verify else None)
+                else:
+                    resp, _, status = self.store.process_wire_batch(
+                        msgs, times, challenges=chal if self.verify else None)
             except GvsError as e:
                 if e.code == abi.GVS_ERR_BATCH_OVERFLOW:
                     # nothing was applied: the callers may retry

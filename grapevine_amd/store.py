@@ -35,6 +35,8 @@ EXPORTED = (
     "gvs_wire_encode_device", "gvs_sr25519_verify", "gvs_sr25519_verify_device",
     "gvs_host_alloc", "gvs_host_free", "gvs_process_wire_batches",
     "gvs_ed25519_verify", "gvs_ed25519_verify_device",
+    "gvs_challenge_derive", "gvs_challenge_derive_device", "gvs_process_wire_batch_seeded",
+    "gvs_process_wire_batch_seeded_device", "gvs_process_wire_batches_seeded",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -75,6 +77,13 @@ def load_library(path=None):
     lib.gvs_process_wire_batches.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp,
                                              ctypes.POINTER(u32)]
     lib.gvs_process_wire_batch_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, u32, vp, vp, vp]
+    lib.gvs_process_wire_batch_seeded.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    lib.gvs_process_wire_batches_seeded.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp,
+                                                    vp, ctypes.POINTER(u32)]
+    lib.gvs_process_wire_batch_seeded_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, vp, u32, vp, vp,
+                                                         vp, vp]
+    lib.gvs_challenge_derive.argtypes = [vp, vp, vp, u32, vp]
+    lib.gvs_challenge_derive_device.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_sr25519_verify.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp]
     lib.gvs_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
     lib.gvs_host_free.argtypes = [vp, vp]
@@ -321,6 +330,86 @@ class ObliviousStore:
             chal.ctypes.data if chal is not None else None, out.ctypes.data, out_stride,
             out_lens.ctypes.data, sigs.ctypes.data, status.ctypes.data))
         return [out[k, :out_lens[k]].tobytes() for k in range(n)], sigs, status
+
+    @staticmethod
+    def _seeds_draws(seeds, draws, n):
+        """(n, 32) uint8 seeds and (n,) uint64 draw indices, or (None, None);
+        one without the other is passed on for the library to refuse."""
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, np.uint8).reshape(n, 32)
+        if draws is not None:
+            draws = np.ascontiguousarray(draws, np.uint64).reshape(n)
+        return seeds, draws
+
+    def process_wire_batch_seeded(self, msgs, times, seeds, draws, in_stride=None,
+                                  out_stride=abi.WIRE_RESPONSE_BYTES):
+        """process_wire_batch with the challenges derived on the device
+        (gvs_process_wire_batch_seeded): request k must sign draw number
+        draws[k] of ChaCha20Rng(seeds[k]) (`challenge_derive`).  seeds (n, 32)
+        uint8 and draws (n,) uint64, or both None (no check).  -> (list of
+        response bytes, (n, 64) signatures, per-request GVS_WIRE_* status,
+        (n, 32) derived challenges; zero when nothing was derived)."""
+        slab, lens, stride = self._wire_slab(msgs, in_stride)
+        n = len(lens)
+        times = np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.uint64), (n,)))
+        out = np.zeros((n, out_stride), np.uint8)
+        out_lens = np.zeros(n, np.uint32)
+        sigs = np.zeros((n, 64), np.uint8)
+        status = np.zeros(n, np.uint32)
+        chal = np.zeros((n, 32), np.uint8)
+        seeds, draws = self._seeds_draws(seeds, draws, n)
+        self._check(self.lib.gvs_process_wire_batch_seeded(
+            self.h, slab.ctypes.data, stride, lens.ctypes.data, n, times.ctypes.data,
+            seeds.ctypes.data if seeds is not None else None,
+            draws.ctypes.data if draws is not None else None, out.ctypes.data, out_stride,
+            out_lens.ctypes.data, sigs.ctypes.data, status.ctypes.data, chal.ctypes.data))
+        return [out[k, :out_lens[k]].tobytes() for k in range(n)], sigs, status, chal
+
+    def process_wire_batches_seeded(self, batches, times, seeds, draws, in_stride=None,
+                                    out_stride=abi.WIRE_RESPONSE_BYTES):
+        """process_wire_batches with the challenges derived on the device
+        (gvs_process_wire_batches_seeded); seeds / draws per message over all
+        batches.  -> list of (response bytes list, status array, (c, 32)
+        derived challenges) per batch.  On a failing batch raises GvsError
+        with `.applied`."""
+        counts = np.array([len(b) for b in batches], dtype=np.uint32)
+        flat = [m for b in batches for m in b]
+        n = len(flat)
+        slab, lens, stride = self._wire_slab(flat, in_stride)
+        times = np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.uint64), (n,)))
+        out = np.zeros((n, out_stride), np.uint8)
+        out_lens = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.uint32)
+        chal = np.zeros((n, 32), np.uint8)
+        seeds, draws = self._seeds_draws(seeds, draws, n)
+        applied = ctypes.c_uint32(0)
+        rc = self.lib.gvs_process_wire_batches_seeded(
+            self.h, slab.ctypes.data, stride, lens.ctypes.data, counts.ctypes.data, len(counts),
+            times.ctypes.data, seeds.ctypes.data if seeds is not None else None,
+            draws.ctypes.data if draws is not None else None, out.ctypes.data, out_stride,
+            out_lens.ctypes.data, status.ctypes.data, chal.ctypes.data, ctypes.byref(applied))
+        if rc != 0:
+            err = GvsError(rc, (self.lib.gvs_last_error(self.h) or b"").decode())
+            err.applied = applied.value
+            raise err
+        res, o = [], 0
+        for c in counts:
+            res.append(([out[k, :out_lens[k]].tobytes() for k in range(o, o + c)], status[o:o + c],
+                        chal[o:o + c]))
+            o += int(c)
+        return res
+
+    def challenge_derive(self, seeds, draws):
+        """The challenge stream on the device (gvs_challenge_derive): seeds
+        (n, 32) uint8, draws (n,) uint64 -> (n, 32) uint8, row k = draw number
+        draws[k] of ChaCha20Rng(seeds[k])."""
+        draws = np.ascontiguousarray(draws, np.uint64).reshape(-1)
+        n = len(draws)
+        seeds = np.ascontiguousarray(seeds, np.uint8).reshape(n, 32)
+        out = np.zeros((n, 32), np.uint8)
+        self._check(self.lib.gvs_challenge_derive(self.h, seeds.ctypes.data, draws.ctypes.data, n,
+                                                  out.ctypes.data))
+        return out
 
     def host_array(self, count, dtype):
         """A numpy array of `count` items in pinned host memory (gvs_host_alloc),

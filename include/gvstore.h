@@ -310,6 +310,46 @@ int gvs_process_wire_batch_device(gvs_handle *h, const void *d_in, uint32_t in_s
                                   const uint32_t *d_in_lens, uint32_t n, const uint64_t *d_times,
                                   const void *d_challenges, void *d_out, uint32_t out_stride,
                                   uint32_t *d_out_lens, void *d_sigs, uint32_t *d_decode_status);
+/* The three wire calls with the challenges derived on the device
+ * (README.md:187-200: each attested connection has a 32-byte seed, and
+ * request i on it signs bytes [32i, 32i+32) of ChaCha20Rng(seed): 20 rounds,
+ * a 64-bit block counter from 0, stream 0).  seeds[k] (32 B) is the seed of
+ * request k's connection and draws[k] its index i on that connection; the
+ * challenge is gvs_challenge_derive's, and everything else is the explicit
+ * call's (the schnorrkel or GVS_FLAG_ED25519_AUTH check, sharded handles,
+ * stop at the first failing batch).  seeds and draws are both given or both
+ * NULL (no check, as challenges = NULL); one without the other is
+ * GVS_ERR_INVALID_ARG.  challenges_out (optional, n x 32 B; all batches'
+ * consecutive) receives the derived challenges, so that a caller can log or
+ * replay a batch; unapplied batches' are zeroed.  Device pointers to seeds and
+ * challenges_out are 16-byte aligned. */
+int gvs_process_wire_batch_seeded(gvs_handle *h, const uint8_t *in, uint32_t in_stride,
+                                  const uint32_t *in_lens, uint32_t n, const uint64_t *times,
+                                  const uint8_t *seeds, const uint64_t *draws, uint8_t *out,
+                                  uint32_t out_stride, uint32_t *out_lens, uint8_t *sigs,
+                                  uint32_t *decode_status, uint8_t *challenges_out);
+int gvs_process_wire_batches_seeded(gvs_handle *h, const uint8_t *in, uint32_t in_stride,
+                                    const uint32_t *in_lens, const uint32_t *counts, uint32_t k,
+                                    const uint64_t *times, const uint8_t *seeds,
+                                    const uint64_t *draws, uint8_t *out, uint32_t out_stride,
+                                    uint32_t *out_lens, uint32_t *decode_status,
+                                    uint8_t *challenges_out, uint32_t *applied);
+int gvs_process_wire_batch_seeded_device(gvs_handle *h, const void *d_in, uint32_t in_stride,
+                                         const uint32_t *d_in_lens, uint32_t n,
+                                         const uint64_t *d_times, const void *d_seeds,
+                                         const uint64_t *d_draws, void *d_out, uint32_t out_stride,
+                                         uint32_t *d_out_lens, void *d_sigs,
+                                         uint32_t *d_decode_status, void *d_challenges_out);
+/* The challenge stream alone: out[k] (32 B) = draw number draws[k] of
+ * ChaCha20Rng(seeds[k]), that is bytes [32*(d&1), 32*(d&1)+32) of ChaCha20
+ * block d >> 1 under key seeds[k] (rand_chacha's layout: 64-bit block counter,
+ * stream 0).  seeds: n x 32 B, draws: n u64, out: n x 32 B, all contiguous;
+ * device pointers 16-byte aligned.  One thread per request, the same
+ * instruction stream whatever the inputs; synchronous on the handle's stream. */
+int gvs_challenge_derive(gvs_handle *h, const uint8_t *seeds, const uint64_t *draws, uint32_t n,
+                         uint8_t *out);
+int gvs_challenge_derive_device(gvs_handle *h, const void *d_seeds, const uint64_t *d_draws,
+                                uint32_t n, void *d_out);
 /* The codec alone, device buffers: wire requests -> gvs_request[n] (+ sigs,
  * + per-request GVS_WIRE_* status, both optional); gvs_response[n] -> wire
  * responses.  Synchronous on the handle's stream. */
