@@ -53,6 +53,7 @@ static_assert(sizeof(gvs_omap_result) == 1040, "map result layout (k_out)");
 namespace {
 
 constexpr int kMaxMarks = 24;
+constexpr int kFrontMarks = 5;    // start, copy, meta, sort_s1, gtx
 constexpr uint64_t kExtra = 64;   // per-op records after the B real ones (record B = dry dummy)
 // Authenticated storage binds every sealed row to a 32-bit epoch (one per
 // batch).  A store refuses work well before the epoch could wrap, since a
@@ -73,6 +74,25 @@ uint64_t ld64(const uint8_t* p) {
   for (int i = 7; i >= 0; --i) v = (v << 8) | p[i];
   return v;
 }
+
+// What a batch's request front (k_copy, k_meta, the Key128 sort, the GtxOp
+// scan) leaves for the rest of the batch: the buffers a kernel reads after the
+// table pass, or the next batch's k_m21x reads as its write side, and the host
+// values taken when the front is enqueued.  Plain single-GPU message stores
+// hold two (Engine::fctx), so that batch t + 1's front can run beside batch
+// t's post-pass kernels (gvs_process_batches_device); every other store, and
+// every front enqueued in order on the main stream, uses fctx[0].
+struct Front {
+  uint4* img = nullptr;
+  OpState* ops = nullptr;
+  uint32_t* kinds = nullptr;
+  uint4* idn = nullptr;
+  uint4* mpos = nullptr;
+  uint4* mpid = nullptr;
+  uint4* gtx = nullptr;      // one of gtxb
+  uint32_t stamp = 0;
+  bool fuse = false;         // the previous batch's write pass runs in this batch's k_m21x
+};
 
 // One shard: persistent tables + per-batch scratch for a batch of B ops.
 struct Engine {
@@ -145,6 +165,14 @@ struct Engine {
   // group-slot overflow while the write pass is still to run.
   bool m2_pending = false;
   MArgs m2_args{};
+  // Request fronts (struct Front).  img, ops, kinds, idn, mpos, mpid, gtx and
+  // stamp_run above are those of the batch whose front phase_a2_rest adopted
+  // last; a front itself reads and writes its context only.
+  Front fctx[2];
+  uint32_t fcur = 0;           // the adopted context
+  bool front_overlap = false;  // option "front_overlap"
+  hipStream_t fstream = nullptr;
+  hipEvent_t ev_pass = nullptr, ev_front = nullptr;
   Scal* gscal = nullptr;
   uint4* msnap = nullptr;    // Q*cm x 1 KiB
   uint4* msnapp = nullptr;   // B x 1 KiB (group snapshots by head position)
@@ -279,6 +307,10 @@ struct gvs_handle {
   hipEvent_t ev[kMaxMarks] = {};
   const char* mark_name[kMaxMarks] = {};
   int n_marks = 0;
+  // marks of a front that ran on the side stream (its own "start" first)
+  hipEvent_t fev[kFrontMarks] = {};
+  const char* fmark_name[kFrontMarks] = {};
+  int n_fmarks = 0;
   bool timed = false;
   bool auth = false;         // GVS_FLAG_AUTH_STORAGE
   bool ed_auth = false;      // GVS_FLAG_ED25519_AUTH: the wire path checks Ed25519 signatures
@@ -337,6 +369,16 @@ static void mark(gvs_handle* h, const char* name) {
   if (!h->timed || h->n_marks >= kMaxMarks) return;
   (void)hipEventRecord(h->ev[h->n_marks], h->stream);
   h->mark_name[h->n_marks++] = name;
+}
+
+// a mark of a front on stream s: the main stream's go with the batch's other
+// marks, the side stream's are kept apart (gvs_last_timings never takes a
+// difference across streams)
+static void front_mark(gvs_handle* h, hipStream_t s, const char* name) {
+  if (s == h->stream) return mark(h, name);
+  if (!h->timed || h->n_fmarks >= kFrontMarks) return;
+  (void)hipEventRecord(h->fev[h->n_fmarks], s);
+  h->fmark_name[h->n_fmarks++] = name;
 }
 
 // ------------------------------------------------------------------ creation
@@ -551,6 +593,8 @@ static SealCtx seal_of(const gvs_handle* h, const Engine& e) {
   return c;
 }
 
+static bool defer_m2(const gvs_handle* h);
+
 static int engine_init(gvs_handle* h, Engine& e, uint32_t shard, uint32_t B) {
   const gvs_config* cfg = &h->cfg;
   e.shard = shard;
@@ -667,6 +711,21 @@ static int engine_init(gvs_handle* h, Engine& e, uint32_t shard, uint32_t B) {
     A(gtx_agg, B / kScanT);
     A(gtx_carry, B / kScanT);
   }
+  e.fctx[0] = Front{e.img, e.ops, e.kinds, e.idn, e.mpos, e.mpid, e.gtx, 0u, false};
+  if (defer_m2(h)) {  // the second front context and what forks a front off the main stream
+    Front& f = e.fctx[1];
+    A(fctx[1].img, (B + E) * 64);
+    A(fctx[1].ops, B);
+    A(fctx[1].kinds, B);
+    A(fctx[1].idn, (uint64_t)B * 8);
+    A(fctx[1].mpos, B);
+    A(fctx[1].mpid, B);
+    GVS_HIP(h, hipMemsetAsync(f.img + (uint64_t)B * 64, 0, E * 1024, h->stream));
+    GVS_HIP(h, hipStreamCreateWithFlags(&e.fstream, hipStreamNonBlocking));
+    GVS_HIP(h, hipEventCreateWithFlags(&e.ev_pass, hipEventDisableTiming));
+    GVS_HIP(h, hipEventCreateWithFlags(&e.ev_front, hipEventDisableTiming));
+    e.front_overlap = true;
+  }
 #undef A
   hipStream_t s = h->stream;
   GVS_HIP(h, hipMemsetAsync(e.img + (uint64_t)B * 64, 0, E * 1024, s));
@@ -765,6 +824,9 @@ static int create_common(const gvs_config* cfg, Mode mode, const uint8_t* comm_i
     return fail(GVS_ERR_DEVICE);
   for (auto& e : h->ev)
     if (hipEventCreate(&e) != hipSuccess) return fail(GVS_ERR_DEVICE);
+  if (defer_m2(h))
+    for (auto& e : h->fev)
+      if (hipEventCreate(&e) != hipSuccess) return fail(GVS_ERR_DEVICE);
   if (h->auth) {
     uint32_t te0[256], nh[kNhWords];
     storage_ctx(cfg->secret_key, h->sc, te0, nh);
@@ -839,15 +901,16 @@ static void sort_tiles(hipStream_t s, K* d, uint32_t n) {
 // for a 64K batch instead of 8-16, which outweighs the extra global steps
 // (C3: both sorts 0.23 -> 0.145 ms per batch, profiles/r03n_pass_ab.txt)
 template <typename K, int EMAX>
-static int sort_keys(gvs_handle* h, K* d, uint32_t n) {
+static int sort_keys(gvs_handle* h, K* d, uint32_t n, hipStream_t s = nullptr) {
   if (n < 1024 || n % 1024) return GVS_ERR_INTERNAL;
+  if (!s) s = h->stream;
   uint32_t e = EMAX;  // the largest tile that divides n
   while ((n / 1024) % e) e >>= 1;
   switch (e) {
-    case 1: sort_tiles<K, 1>(h->stream, d, n); break;
-    case 2: sort_tiles<K, 2>(h->stream, d, n); break;
-    case 4: sort_tiles<K, (EMAX < 4 ? EMAX : 4)>(h->stream, d, n); break;
-    default: sort_tiles<K, EMAX>(h->stream, d, n); break;
+    case 1: sort_tiles<K, 1>(s, d, n); break;
+    case 2: sort_tiles<K, 2>(s, d, n); break;
+    case 4: sort_tiles<K, (EMAX < 4 ? EMAX : 4)>(s, d, n); break;
+    default: sort_tiles<K, EMAX>(s, d, n); break;
   }
   GVS_HIP(h, hipGetLastError());
   return GVS_OK;
@@ -957,41 +1020,72 @@ static void launch_sjoint(gvs_handle* h, Engine& e) {
                      (const uint4*)e.tbuf[e.par], e.stamp_prev, e.stamp_run, e.W, e.S, e.c, kSpBufs, e.scal);
 }
 
-// Phase A of pipeline 2: phase_a's kernels, then allocation, the message-pass
-// sort and the transaction slots (k_rtx), so that every fixed-capacity check
-// (mailbox groups, transaction slots) is decided before any state changes.
-static int phase_a2(gvs_handle* h, Engine& e, const uint4* d_in, uint32_t stride, uint32_t n) {
-  hipStream_t s = h->stream;
-  const uint32_t B = e.B, nblk = e.nblk;
-  e.stamp_run = e.stamp_next++;
+// The request front of a batch, on stream s into front context ci: k_copy,
+// k_meta, the Key128 sort and the GtxOp scan.  It reads the requests and, with
+// the expiry sweep on, the records xprev of the previous table pass; it writes
+// context ci, front-only scratch (types, s1keys, gtx_agg, gtx_carry), the
+// stamped lines of the context's gtx buffer, and one error word: a group-slot
+// overflow sets bit 1 of gscal->error when fuse (folded into the batch's own
+// word after its k_m21x), else of scal->error.  It takes no host state from
+// the Engine but the stamp counter and the gtx ping-pong, both its own to
+// advance, so it may be enqueued before the previous batch's phase_b2.
+static int front(gvs_handle* h, Engine& e, uint32_t ci, hipStream_t s, const uint4* d_in, uint32_t stride,
+                 uint32_t n, bool fuse, const uint4* xprev) {
+  Front& f = e.fctx[ci];
+  const uint32_t B = e.B;
+  f.stamp = e.stamp_next++;
   if (e.stamp_next == kNone) e.stamp_next = 1;
   const uint32_t xbase = B - e.X;
   // this batch's group descriptors; a deferred write pass of the previous
   // batch still reads the other buffer
-  e.gtx = e.gtxb[e.gsel];
+  f.gtx = e.gtxb[e.gsel];
   e.gsel ^= 1u;
-  const bool fuse = e.m2_pending;
-  hipLaunchKernelGGL(k_copy, dim3(B / (4 * kCopyPerWave)), dim3(256), 0, s, d_in, stride, n, B, e.img, e.types,
-                     (const uint4*)(e.X ? e.xb2[e.par ^ 1] : nullptr), xbase);
-  mark(h, "copy");
+  f.fuse = fuse;
+  hipLaunchKernelGGL(k_copy, dim3(B / (4 * kCopyPerWave)), dim3(256), 0, s, d_in, stride, n, B, f.img, e.types,
+                     xprev, xbase);
+  front_mark(h, s, "copy");
   {
-    MetaArgs a{e.img, e.types, e.ops, e.kinds, e.s1keys, n, B, e.Q, e.logQ, e.N, e.kc, xbase, e.idn};
+    MetaArgs a{f.img, e.types, f.ops, f.kinds, e.s1keys, n, B, e.Q, e.logQ, e.N, e.kc, xbase, f.idn};
     // one op per thread, no block-level work: 256-thread workgroups spread
     // the batch over every CU (1024-thread ones filled a quarter of them)
     hipLaunchKernelGGL(k_meta, dim3(B / 256), dim3(256), 0, s, a);
   }
-  mark(h, "meta");
-  if (int r = sort_keys<Key128, 1>(h, e.s1keys, B)) return r;
-  mark(h, "sort_s1");
+  front_mark(h, s, "meta");
+  if (int r = sort_keys<Key128, 1>(h, e.s1keys, B, s)) return r;
+  front_mark(h, s, "sort_s1");
   {
-    GtxArgs a{e.s1keys, e.ops, e.mpos, e.gtx, e.gtx_agg, e.gtx_carry, fuse ? e.gscal : e.scal,
-              B,        e.Q,   e.logQ, e.cm,  B / kScanT, e.stamp_run};
-    a.mpid = e.mpid;
+    GtxArgs a{e.s1keys, f.ops, f.mpos, f.gtx, e.gtx_agg, e.gtx_carry, fuse ? e.gscal : e.scal,
+              B,        e.Q,   e.logQ, e.cm,  B / kScanT, f.stamp};
+    a.mpid = f.mpid;
     hipLaunchKernelGGL(k_scan_a<GtxOp>, dim3(B / kScanT), dim3(kScanT), 0, s, a);
     hipLaunchKernelGGL(k_scan_b<GtxOp>, dim3(1), dim3(kScanT), 0, s, a);
     hipLaunchKernelGGL(k_scan_c<GtxOp>, dim3(B / kScanT), dim3(kScanT), 0, s, a);
   }
-  mark(h, "gtx");
+  front_mark(h, s, "gtx");
+  GVS_HIP(h, hipGetLastError());
+  return GVS_OK;
+}
+
+// The rest of phase A of pipeline 2, after the front of context ci: the
+// mailbox read pass, then allocation, the message-pass sort and the
+// transaction slots (k_rtx), so that every fixed-capacity check (mailbox
+// groups, transaction slots) is decided before any state changes.  The
+// context becomes the Engine's current one: every later kernel of the batch
+// takes its buffers and its stamp from there.
+static int phase_a2_rest(gvs_handle* h, Engine& e, uint32_t ci) {
+  hipStream_t s = h->stream;
+  const uint32_t B = e.B, nblk = e.nblk;
+  const Front& f = e.fctx[ci];
+  e.fcur = ci;
+  e.img = f.img;
+  e.ops = f.ops;
+  e.kinds = f.kinds;
+  e.idn = f.idn;
+  e.mpos = f.mpos;
+  e.mpid = f.mpid;
+  e.gtx = f.gtx;
+  e.stamp_run = f.stamp;
+  const bool fuse = f.fuse;
   if (h->auth) {
     hipLaunchKernelGGL(k_m1a, dim3(e.Q), dim3(256), (e.cm + 1) * sizeof(GroupM) + GVS_MA_EXTRA_LDS, s, margs2(h, e));
   } else if (fuse) {
@@ -1041,6 +1135,14 @@ static int phase_a2(gvs_handle* h, Engine& e, const uint4* d_in, uint32_t stride
   mark(h, "rtx");
   GVS_HIP(h, hipGetLastError());
   return GVS_OK;
+}
+
+// Phase A with the front in order on the main stream, in context 0.
+static int phase_a2(gvs_handle* h, Engine& e, const uint4* d_in, uint32_t stride, uint32_t n) {
+  if (int r = front(h, e, 0, h->stream, d_in, stride, n, e.m2_pending,
+                    (const uint4*)(e.X ? e.xb2[e.par ^ 1] : nullptr)))
+    return r;
+  return phase_a2_rest(h, e, 0);
 }
 
 // The message-table pass of the fixed-slot pipeline (also the block and
@@ -1106,11 +1208,16 @@ static void launch_rpass2(gvs_handle* h, Engine& e) {
 // stores run it at the end of the batch.
 static bool defer_m2(const gvs_handle* h) { return h->mode == kSingle && !h->auth && h->kind == 0; }
 
-static int phase_b2(gvs_handle* h, Engine& e, uint32_t n, uint4* d_out) {
-  hipStream_t s = h->stream;
-  const uint32_t B = e.B, nblk = e.nblk;
+static void phase_b2_pass(gvs_handle* h, Engine& e) {
   launch_rpass2(h, e);
   mark(h, "rpass");
+}
+
+// after the table pass: the response chain, the free ring, the mailbox write
+// pass (or its deferral) and the responses out
+static int phase_b2_post(gvs_handle* h, Engine& e, uint32_t n, uint4* d_out) {
+  hipStream_t s = h->stream;
+  const uint32_t B = e.B, nblk = e.nblk;
   {
     Rr1Args a{e.rpos, e.rop, e.rsb, e.rr1_agg, e.rr1_carry, e.scal, B, B / kScanT, B - e.X, e.S,
               e.rr1g, 0u, e.idn, e.snapidp};
@@ -1178,6 +1285,11 @@ static int phase_b2(gvs_handle* h, Engine& e, uint32_t n, uint4* d_out) {
   mark(h, "m2");
   GVS_HIP(h, hipGetLastError());
   return GVS_OK;
+}
+
+static int phase_b2(gvs_handle* h, Engine& e, uint32_t n, uint4* d_out) {
+  phase_b2_pass(h, e);
+  return phase_b2_post(h, e, n, d_out);
 }
 
 
@@ -1276,10 +1388,54 @@ static int run_batch_body(gvs_handle* h, const uint4* d_in, uint32_t n, uint4* d
 static int run_batch(gvs_handle* h, const uint4* d_in, uint32_t n, uint4* d_out,
                      bool reset = true) {
   h->n_marks = 0;
+  h->n_fmarks = 0;
   mark(h, "start");
   if (reset)
     if (int r = reset_errors(h)) return r;
   return run_batch_body(h, d_in, n, d_out);
+}
+
+// The front of the batch after the one being enqueued, forked off the main
+// stream behind the table pass just enqueued there: the side stream waits for
+// the pass, runs the front into the context the current batch does not use,
+// and records ev_front, which the main stream waits on before that batch's
+// phase_a2_rest (join_front).  The pass itself runs alone, as in a
+// single-batch call; the front runs beside the post-pass kernels, which are
+// small launches that leave most of the chip idle.  The
+// order of all of it is fixed by the two events, whatever the requests hold.
+//
+// The front is enqueued before the current batch's phase_b2_post has run on
+// the host, so it takes what that would set: a write pass to fuse with (the
+// store defers every batch's) and, for the expiry records, the parity the
+// pass just enqueued wrote at (par flips when the batch is counted).
+static int fork_front(gvs_handle* h, Engine& e, const uint4* d_in, uint32_t n) {
+  GVS_HIP(h, hipEventRecord(e.ev_pass, h->stream));
+  GVS_HIP(h, hipStreamWaitEvent(e.fstream, e.ev_pass, 0));
+  h->n_fmarks = 0;
+  front_mark(h, e.fstream, "start");
+  const int r = front(h, e, e.fcur ^ 1u, e.fstream, d_in, kAbiU4, n, true,
+                      (const uint4*)(e.X ? e.xb2[e.par] : nullptr));
+  // recorded even behind a front that stopped half-way: the join must cover
+  // whatever of it reached the stream
+  GVS_HIP(h, hipEventRecord(e.ev_front, e.fstream));
+  return r;
+}
+
+// The main stream goes on only after the forked front.  With `adopt` false
+// the front's batch is not going to run (an earlier one was not enqueued
+// whole): what the front left on the device is scratch of its own context,
+// gtx lines under a stamp that no batch will carry (stamps are not reused, and
+// k_m21x takes only lines of its batch's stamp), and possibly bit 1 of
+// gscal->error, which no k_err_fold is coming for and which is cleared here.
+// The context parity needs no repair: a front on the main stream always takes
+// context 0, and a forked one the context its predecessor does not use.
+static int join_front(gvs_handle* h, Engine& e, bool adopt) {
+  GVS_HIP(h, hipStreamWaitEvent(h->stream, e.ev_front, 0));
+  if (!adopt) {
+    h->n_fmarks = 0;
+    GVS_HIP(h, hipMemsetAsync(&e.gscal->error, 0, sizeof(uint32_t), h->stream));
+  }
+  return GVS_OK;
 }
 
 static int run_batch_body(gvs_handle* h, const uint4* d_in, uint32_t n, uint4* d_out) {
@@ -1699,6 +1855,13 @@ int gvs_destroy(gvs_handle* h) {
   if (!h) return GVS_ERR_INVALID_ARG;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (auto& e : h->eng) {
+    if (e.fstream) (void)hipStreamSynchronize(e.fstream), (void)hipStreamDestroy(e.fstream);
+    if (e.ev_pass) (void)hipEventDestroy(e.ev_pass);
+    if (e.ev_front) (void)hipEventDestroy(e.ev_front);
+  }
+  for (auto& e : h->fev)
+    if (e) (void)hipEventDestroy(e);
   if (h->comm) (void)ncclCommDestroy(h->comm);
   HostPipe& hp = h->pipe;
   if (hp.copy) (void)hipStreamSynchronize(hp.copy);
@@ -2027,26 +2190,61 @@ int gvs_process_batches_device(gvs_handle* h, const void* d_reqs, const uint32_t
   uint32_t enq = 0;
   int stop = GVS_OK;
   // every batch enqueued back to back; the error word is not reset between
-  // them, so the batches behind a failing one do nothing
+  // them, so the batches behind a failing one do nothing (a forked front of
+  // such a batch still runs, into what fork_front and join_front name)
+  Engine& e0 = h->eng[0];
+  const bool ov = defer_m2(h) && e0.front_overlap;
+  bool forked = false;  // the next batch's front is on the side stream
   for (uint32_t t = 0; t < k; ++t) {
     if (int r = check_epoch(h)) {
       stop = r;
       break;
     }
     snap[t] = save_state(h);
-    int r = run_batch(h, in + off * kAbiU4, counts[t], out + off * kAbiU4, false);
-    if (!r && h->mode != kSingle) r = agree_errors(h);
-    if (r) {  // batch t was not (wholly) enqueued: the ones before it still count
+    const uint4* in_t = in + off * kAbiU4;
+    uint4* out_t = out + off * kAbiU4;
+    int r, fr = GVS_OK;
+    if (!ov) {
+      r = run_batch(h, in_t, counts[t], out_t, false);
+      if (!r && h->mode != kSingle) r = agree_errors(h);
+    } else {
+      h->n_marks = 0;
+      mark(h, "start");
+      if (forked) {
+        r = join_front(h, e0, true);
+        forked = false;
+        if (!r) r = phase_a2_rest(h, e0, e0.fcur ^ 1u);
+      } else {
+        h->n_fmarks = 0;
+        r = phase_a2(h, e0, in_t, kAbiU4, counts[t]);
+      }
+      if (!r) {
+        phase_b2_pass(h, e0);
+        if (t + 1 < k) {
+          fr = fork_front(h, e0, in_t + (uint64_t)counts[t] * kAbiU4, counts[t + 1]);
+          forked = true;
+        }
+        r = phase_b2_post(h, e0, counts[t], out_t);
+      }
+    }
+    hipError_t ce = hipSuccess;
+    if (!r)
+      ce = hipMemcpyAsync(&p.errs[t], &e0.scal->error, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+    if (r || ce != hipSuccess) {  // batch t was not (wholly) enqueued: the ones before it still count
       restore_state(h, snap[t]);
-      stop = r;
+      stop = r ? r : GVS_ERR_DEVICE;
+      if (!r) h->err = std::string("hipMemcpyAsync(errs): ") + hipGetErrorString(ce);
       break;
     }
-    GVS_HIP(h, hipMemcpyAsync(&p.errs[t], &h->eng[0].scal->error, sizeof(uint32_t),
-                              hipMemcpyDeviceToHost, h->stream));
     advance(h);  // as if applied; rolled back below if it was not
     off += counts[t];
     enq = t + 1;
+    if (fr) {  // the next batch's front was not (wholly) enqueued
+      stop = fr;
+      break;
+    }
   }
+  if (forked) (void)join_front(h, e0, false);  // a front whose batch is not going to run
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   off = 0;
   for (uint32_t t = 0; t < enq; ++t) {
@@ -2804,7 +3002,11 @@ int gvs_get_option(gvs_handle* h, const char* key, int64_t* value) {
     int r = -1;
     if (h->comm && ncclCommUserRank(h->comm, &r) != ncclSuccess) return GVS_ERR_DEVICE;
     *value = r;
-  } else return GVS_ERR_INVALID_ARG;
+  } else if (std::strcmp(key, "front_overlap") == 0)
+    // 1: in a K-batch device call the request front of batch t + 1 runs on a
+    // side stream beside batch t's post-pass kernels (fork_front)
+    *value = e.front_overlap ? 1 : 0;
+  else return GVS_ERR_INVALID_ARG;
   return GVS_OK;
 }
 
@@ -2812,6 +3014,10 @@ int gvs_set_option(gvs_handle* h, const char* key, int64_t value) {
   if (!h || !key) return GVS_ERR_INVALID_ARG;
   if (std::strcmp(key, "sealed_pass_waves") == 0 && (value == 0 || value == 4 || value == 8 || value == 12)) {
     h->sealed_nw = (int)value;
+    return GVS_OK;
+  }
+  if (std::strcmp(key, "front_overlap") == 0 && (value == 0 || value == 1) && h->kind == 0 && defer_m2(h)) {
+    h->eng[0].front_overlap = value != 0;
     return GVS_OK;
   }
   return GVS_ERR_INVALID_ARG;
@@ -2823,6 +3029,15 @@ int gvs_last_timings(gvs_handle* h, const char** names, float* ms, int cap) {
   if (!h->timed) return 0;
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   int c = 0;
+  // a front that ran on the side stream (the last batch of a K-batch device
+  // call): its stages between its own marks there, then the main stream's;
+  // the batch's first main-stream stage holds the wait for the front
+  for (int i = 0; i + 1 < h->n_fmarks && c < cap; ++i, ++c) {
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, h->fev[i], h->fev[i + 1]);
+    if (names) names[c] = h->fmark_name[i + 1];
+    if (ms) ms[c] = t;
+  }
   for (int i = 0; i + 1 < h->n_marks && c < cap; ++i, ++c) {
     float t = 0.f;
     (void)hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]);
