@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <thread>
@@ -212,14 +213,22 @@ struct Router {
 
 }  // namespace
 
-// Double-buffered host path (gvs_process_batches): pinned host staging, two
-// device staging pairs, a copy stream and per-slot events.
+// One array that travels with the batches of a pipelined host call (pipe_run):
+// per slot, the device buffer a batch's kernels see and the pinned staging
+// buffer pageable caller memory goes through.
+struct PipeBuf {
+  void* dev[2] = {};
+  void* pin[2] = {};
+};
+
+// Double-buffered host calls (gvs_process_batches, gvs_process_wire_batches):
+// the request and response buffers of the former, and what every pipelined
+// call shares: two copy streams, the per-slot events and the pinned error
+// words.  The calls on a handle are serial and synchronous, so one set serves
+// them all.
 struct HostPipe {
   bool ready = false;
-  uint4* din[2] = {};
-  uint4* dout[2] = {};
-  uint8_t* hin[2] = {};
-  uint8_t* hout[2] = {};
+  PipeBuf in, out;           // gvs_request / gvs_response
   uint32_t* herr = nullptr;  // pinned: the agreed error word of the batch in each slot
   uint32_t* errs = nullptr;  // pinned: one error word per batch of gvs_process_batches_device
   uint32_t nerr = 0;
@@ -244,27 +253,18 @@ struct WireStage {
   uint64_t* draws = nullptr; // seeded calls: n draw indices
 };
 
-// Double-buffered wire path (gvs_process_wire_batches): per slot, the device
-// and pinned host buffers of one batch's wire messages and results, allocated
-// on first use for max_submit messages of kWireSlotMax bytes each way.
+// Double-buffered wire path (gvs_process_wire_batches): one batch's wire
+// messages and results per slot, allocated on first use for max_submit
+// messages of kWireSlotMax bytes each way.
 struct WirePipe {
   bool ready = false;
-  uint8_t *din[2] = {}, *dout[2] = {};
-  uint32_t *dlens[2] = {}, *dolens[2] = {}, *dstat[2] = {};
-  uint64_t* dtimes[2] = {};
-  uint4* dchal[2] = {};
-  uint8_t *hin[2] = {}, *hout[2] = {}, *hchal[2] = {};
-  uint32_t *hlens[2] = {}, *holens[2] = {}, *hstat[2] = {};
-  uint64_t* htimes[2] = {};
-  hipEvent_t h2d[2] = {}, done[2] = {}, d2h[2] = {};
+  PipeBuf in, lens, times, chal, out, olens, stat;
   // seeded calls (gvs_process_wire_batches_seeded), allocated on their first
   // use: seeds and draw indices go up where the challenges would, and the
-  // challenges derived into dchal[b] come down with the results
+  // challenges derived into chal.dev[b] come down through chout (its dev is
+  // chal's)
   bool seeded = false;
-  uint4* dseed[2] = {};
-  uint64_t* ddraw[2] = {};
-  uint8_t *hseed[2] = {}, *hchout[2] = {};
-  uint64_t* hdraw[2] = {};
+  PipeBuf seed, draw, chout;
 };
 
 // Pinned bounce buffers of the single-call host APIs (gvs_process_batch, the
@@ -276,9 +276,10 @@ struct WirePipe {
 // (DESIGN.md §3 "Counters").  Pageable caller memory is therefore copied by
 // the host into grow-only pinned buffers and moved by DMA from there.
 struct Bounce {
-  static constexpr int kSlots = 10;  // 0..3 and 8 in, 4..7 and 9 out
+  static constexpr int kSlots = 10;  // the seeded wire batch: 5 in, 5 out
   void* buf[kSlots] = {};
   size_t cap[kSlots] = {};
+  int used = 0;  // slots taken by this call's copies, in order (bounce_begin: 0)
   struct Out {
     void* dst;
     int slot;
@@ -1833,6 +1834,43 @@ struct gvs_omap {
   gvs_handle* h = nullptr;
 };
 
+// ------------------------------------- host-call helpers (templates: C++ linkage)
+
+// The fields sr::SrArgs and sr::EdArgs share: where the keys, messages and
+// signatures are, and where the verdicts go (`ok`: a word per signature; the
+// wire path's `reqs` slab and `status` words).
+template <typename Args>
+static void verify_fields(Args& a, const void* pk, uint32_t pk_stride, const void* msg, uint32_t msg_stride,
+                          uint32_t msg_len, const void* sig, uint32_t sig_stride, uint32_t n, uint32_t* ok,
+                          uint4* reqs, uint32_t* status) {
+  a.pk = (const uint8_t*)pk;
+  a.pk_stride = pk_stride;
+  a.msg = (const uint8_t*)msg;
+  a.msg_stride = msg_stride;
+  a.msg_len = msg_len;
+  a.sig = (const uint8_t*)sig;
+  a.sig_stride = sig_stride;
+  a.n = n;
+  a.ok = ok;
+  a.reqs = reqs;
+  a.status = status;
+}
+
+// A stand-alone launch, synchronous on the handle's stream.  With a `name`
+// the call has stage marks of its own: "start", then `name`.
+template <typename Enqueue>
+static int launch_sync(gvs_handle* h, const char* name, Enqueue enqueue) {
+  if (name) {
+    h->n_marks = 0;
+    mark(h, "start");
+  }
+  enqueue();
+  if (name) mark(h, name);
+  GVS_HIP(h, hipGetLastError());
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return GVS_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 
 extern "C" {
@@ -1866,27 +1904,20 @@ int gvs_destroy(gvs_handle* h) {
   HostPipe& hp = h->pipe;
   if (hp.copy) (void)hipStreamSynchronize(hp.copy);
   if (hp.copy_out) (void)hipStreamSynchronize(hp.copy_out);
-  for (int b = 0; b < 2; ++b) {
-    if (hp.hin[b]) (void)hipHostFree(hp.hin[b]);
-    if (hp.hout[b]) (void)hipHostFree(hp.hout[b]);
+  WirePipe& wp = h->wpipe;
+  for (PipeBuf* c : {&hp.in, &hp.out, &wp.in, &wp.lens, &wp.times, &wp.chal, &wp.out, &wp.olens, &wp.stat,
+                     &wp.seed, &wp.draw, &wp.chout})
+    for (void* q : c->pin)
+      if (q) (void)hipHostFree(q);
+  for (int b = 0; b < 2; ++b)
     for (hipEvent_t ev : {hp.h2d[b], hp.done[b], hp.d2h[b]})
       if (ev) (void)hipEventDestroy(ev);
-  }
   if (hp.herr) (void)hipHostFree(hp.herr);
   if (hp.errs) (void)hipHostFree(hp.errs);
   for (void* q : h->bounce.buf)
     if (q) (void)hipHostFree(q);
   if (h->sr_dev) (void)hipFree(h->sr_dev);
   if (h->err_pin) (void)hipHostFree(h->err_pin);
-  WirePipe& wp = h->wpipe;
-  for (int b = 0; b < 2; ++b) {
-    for (void* q : {(void*)wp.hin[b], (void*)wp.hout[b], (void*)wp.hchal[b], (void*)wp.hlens[b],
-                    (void*)wp.holens[b], (void*)wp.hstat[b], (void*)wp.htimes[b], (void*)wp.hseed[b],
-                    (void*)wp.hchout[b], (void*)wp.hdraw[b]})
-      if (q) (void)hipHostFree(q);
-    for (hipEvent_t ev : {wp.h2d[b], wp.done[b], wp.d2h[b]})
-      if (ev) (void)hipEventDestroy(ev);
-  }
   if (hp.copy) (void)hipStreamDestroy(hp.copy);
   if (hp.copy_out) (void)hipStreamDestroy(hp.copy_out);
   for (void* p : h->allocs) (void)hipFree(p);
@@ -1916,8 +1947,8 @@ int gvs_create_sharded(const gvs_config* cfg, const uint8_t comm_id[GVS_COMM_ID_
   return create_common(cfg, kRccl, comm_id, out);
 }
 
-static int h2d(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes);
-static int d2h(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes);
+static int h2d(gvs_handle* h, void* dst, const void* src, size_t bytes);
+static int d2h(gvs_handle* h, void* dst, const void* src, size_t bytes);
 static int bounce_done(gvs_handle* h, int rc);
 static int bounce_begin(gvs_handle* h);
 
@@ -1927,9 +1958,9 @@ int gvs_process_batch(gvs_handle* h, const gvs_request* reqs, uint32_t n, gvs_re
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
   if (int r = bounce_begin(h)) return r;
-  if (int r = h2d(h, 0, h->in_stage, reqs, (size_t)n * sizeof(gvs_request))) return r;
+  if (int r = h2d(h, h->in_stage, reqs, (size_t)n * sizeof(gvs_request))) return r;
   if (int r = run_batch(h, h->in_stage, n, h->out_stage)) return r;
-  if (int r = d2h(h, 4, out, h->out_stage, (size_t)n * sizeof(gvs_response))) return r;
+  if (int r = d2h(h, out, h->out_stage, (size_t)n * sizeof(gvs_response))) return r;
   return bounce_done(h, finish(h));
 }
 
@@ -1968,33 +1999,42 @@ static bool is_pinned(const void* p) {
 // at the entry of a call that uses the bounce slots: wait for the copies of an
 // earlier call that ended on an error path (its slots may still be read or
 // written by the stream) before any slot is rewritten or freed.  Within one
-// call every slot is used once, so a call's own copies never wait here.
+// call every copy takes the next free slot, so a call's own copies never wait
+// here.
 static int bounce_begin(gvs_handle* h) {
   h->bounce.pend.clear();
+  h->bounce.used = 0;
   if (!h->bounce.inflight) return GVS_OK;
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   h->bounce.inflight = false;
   return GVS_OK;
 }
 
-static int bounce_grow(gvs_handle* h, int slot, size_t bytes) {
+// the call's next free bounce slot, holding at least `bytes`
+static int bounce_take(gvs_handle* h, size_t bytes, int* slot) {
   Bounce& b = h->bounce;
-  if (b.cap[slot] >= bytes) return GVS_OK;
-  if (b.buf[slot]) GVS_HIP(h, hipHostFree(b.buf[slot]));
-  b.buf[slot] = nullptr;
-  b.cap[slot] = 0;
+  if (b.used >= Bounce::kSlots) {
+    h->err = "more pageable arrays in one call than bounce slots";
+    return GVS_ERR_INTERNAL;
+  }
+  const int k = *slot = b.used++;
+  if (b.cap[k] >= bytes) return GVS_OK;
+  if (b.buf[k]) GVS_HIP(h, hipHostFree(b.buf[k]));
+  b.buf[k] = nullptr;
+  b.cap[k] = 0;
   const size_t cap = std::max<size_t>(bytes, 1u << 20);
-  GVS_HIP(h, hipHostMalloc(&b.buf[slot], cap, hipHostMallocDefault));
-  b.cap[slot] = cap;
+  GVS_HIP(h, hipHostMalloc(&b.buf[k], cap, hipHostMallocDefault));
+  b.cap[k] = cap;
   return GVS_OK;
 }
 
 // host -> device from caller memory `src`: pinned memory is copied from
-// directly, pageable memory through bounce slot `slot` (0..3, 8)
-static int h2d(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes) {
+// directly, pageable memory through a bounce slot
+static int h2d(gvs_handle* h, void* dst, const void* src, size_t bytes) {
   if (!bytes) return GVS_OK;
   if (!is_pinned(src)) {
-    if (int r = bounce_grow(h, slot, bytes)) return r;
+    int slot;
+    if (int r = bounce_take(h, bytes, &slot)) return r;
     par_memcpy(h->bounce.buf[slot], src, bytes);
     src = h->bounce.buf[slot];
     h->bounce.inflight = true;
@@ -2003,15 +2043,16 @@ static int h2d(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes
   return GVS_OK;
 }
 
-// device -> host into caller memory `dst`: pageable memory through bounce
-// slot `slot` (4..7, 9), handed over by bounce_done after the stream's sync
-static int d2h(gvs_handle* h, int slot, void* dst, const void* src, size_t bytes) {
+// device -> host into caller memory `dst`: pageable memory through a bounce
+// slot, handed over by bounce_done after the stream's sync
+static int d2h(gvs_handle* h, void* dst, const void* src, size_t bytes) {
   if (!bytes) return GVS_OK;
   if (is_pinned(dst)) {
     GVS_HIP(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
     return GVS_OK;
   }
-  if (int r = bounce_grow(h, slot, bytes)) return r;
+  int slot;
+  if (int r = bounce_take(h, bytes, &slot)) return r;
   GVS_HIP(h, hipMemcpyAsync(h->bounce.buf[slot], src, bytes, hipMemcpyDeviceToHost, h->stream));
   h->bounce.inflight = true;
   h->bounce.pend.push_back(Bounce::Out{dst, slot, bytes});
@@ -2041,15 +2082,24 @@ int gvs_host_free(gvs_handle* h, void* p) {
   return GVS_OK;
 }
 
+// both slots of one pipeline array: `bytes` of device and of pinned memory
+// each, or (`alias`) pinned memory alone beside another array's device buffers
+static int pipe_buf(gvs_handle* h, PipeBuf& c, size_t bytes, const PipeBuf* alias = nullptr) {
+  for (int b = 0; b < 2; ++b) {
+    if (alias) c.dev[b] = alias->dev[b];
+    else if (int rc = dalloc(h, &c.dev[b], bytes)) return rc;
+    GVS_HIP(h, hipHostMalloc(&c.pin[b], bytes, hipHostMallocDefault));
+  }
+  return GVS_OK;
+}
+
 static int pipe_init(gvs_handle* h) {
   HostPipe& p = h->pipe;
   if (p.ready) return GVS_OK;
   const uint64_t cap = (uint64_t)h->Bsub * (h->mode == kLocal ? h->S : 1u);
+  if (int rc = pipe_buf(h, p.in, cap * sizeof(gvs_request))) return rc;
+  if (int rc = pipe_buf(h, p.out, cap * sizeof(gvs_response))) return rc;
   for (int b = 0; b < 2; ++b) {
-    if (int rc = dalloc_t(h, &p.din[b], cap * kAbiU4)) return rc;
-    if (int rc = dalloc_t(h, &p.dout[b], cap * kAbiU4)) return rc;
-    GVS_HIP(h, hipHostMalloc((void**)&p.hin[b], cap * sizeof(gvs_request), hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.hout[b], cap * sizeof(gvs_response), hipHostMallocDefault));
     GVS_HIP(h, hipEventCreateWithFlags(&p.h2d[b], hipEventDisableTiming));
     GVS_HIP(h, hipEventCreateWithFlags(&p.done[b], hipEventDisableTiming));
     GVS_HIP(h, hipEventCreateWithFlags(&p.d2h[b], hipEventDisableTiming));
@@ -2061,116 +2111,162 @@ static int pipe_init(gvs_handle* h) {
   return GVS_OK;
 }
 
-// k batches from host memory, double-buffered: batch t+1's requests are
-// staged and copied in, and batch t-1's responses copied out, while batch t
-// runs.  Batches apply in order; the error word is not reset between them,
-// so after a failed batch the following ones enqueued behind it do nothing,
-// and the host state is rolled back to the failed batch.
+// What the K-batch calls check before anything else, and the requests of all
+// k batches together.
+static int batches_begin(gvs_handle* h, bool args_ok, const uint32_t* counts, uint32_t k,
+                         uint32_t* applied, uint64_t* total) {
+  if (applied) *applied = 0;
+  *total = 0;
+  if (!h || h->kind != 0 || !args_ok || (k && !counts)) return GVS_ERR_INVALID_ARG;
+  for (uint32_t t = 0; t < k; ++t) {
+    if (counts[t] > max_submit(h)) return GVS_ERR_INVALID_ARG;
+    *total += counts[t];
+  }
+  return h->poisoned ? GVS_ERR_INTEGRITY : GVS_OK;
+}
+
+// One array of a pipelined call: the caller's pointer, its bytes per request,
+// its direction, and the pipeline buffers it travels through.
+struct Column {
+  void* user;
+  size_t stride;
+  bool out;  // device -> host
+  PipeBuf* buf;
+  bool direct = false;  // pipe_run: caller memory is pinned, copied without staging
+  uint8_t* at(uint64_t off) const { return (uint8_t*)user + off * stride; }
+};
+static Column col_in(const void* user, size_t stride, PipeBuf& buf) {
+  return Column{const_cast<void*>(user), stride, false, &buf};
+}
+static Column col_out(void* user, size_t stride, PipeBuf& buf) { return Column{user, stride, true, &buf}; }
+
+// pipe_run's enqueue step: the batch of n requests whose columns are in the
+// device buffers of slot b, on the engine stream
+using PipeEnqueue = std::function<int(uint32_t b, uint32_t n)>;
+
+// batch t of n requests at request offset `off` into slot b: inputs up on
+// `copy`, the batch on the engine stream, its error word and outputs down on
+// `copy_out`.  The slot's events order the three streams; `reuse`: the slot
+// held batch t-2.
+static int pipe_enqueue(gvs_handle* h, const std::vector<Column>& cols, uint32_t b, bool reuse,
+                        uint64_t off, uint32_t n, const PipeEnqueue& enqueue) {
+  HostPipe& p = h->pipe;
+  hipStream_t s = h->stream;
+  bool staged = false;
+  for (const Column& c : cols) staged |= !c.out && !c.direct;
+  if (reuse && staged) GVS_HIP(h, hipEventSynchronize(p.h2d[b]));  // the staging of slot b is free again
+  for (const Column& c : cols)
+    if (!c.out && !c.direct) par_memcpy(c.buf->pin[b], c.at(off), n * c.stride);
+  if (reuse) GVS_HIP(h, hipStreamWaitEvent(p.copy, p.done[b], 0));  // device slot b consumed
+  for (const Column& c : cols)
+    if (!c.out && n)
+      GVS_HIP(h, hipMemcpyAsync(c.buf->dev[b], c.direct ? c.at(off) : c.buf->pin[b], n * c.stride,
+                                hipMemcpyHostToDevice, p.copy));
+  GVS_HIP(h, hipEventRecord(p.h2d[b], p.copy));
+  GVS_HIP(h, hipStreamWaitEvent(s, p.h2d[b], 0));
+  if (reuse) GVS_HIP(h, hipStreamWaitEvent(s, p.d2h[b], 0));  // results of slot b copied out
+  if (int r = enqueue(b, n)) return r;
+  if (h->mode != kSingle)
+    if (int r = agree_errors(h)) return r;
+  GVS_HIP(h, hipMemcpyAsync(&p.herr[b], &h->eng[0].scal->error, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  GVS_HIP(h, hipEventRecord(p.done[b], s));
+  GVS_HIP(h, hipStreamWaitEvent(p.copy_out, p.done[b], 0));
+  for (const Column& c : cols)
+    if (c.out && n)
+      GVS_HIP(h, hipMemcpyAsync(c.direct ? c.at(off) : c.buf->pin[b], c.buf->dev[b], n * c.stride,
+                                hipMemcpyDeviceToHost, p.copy_out));
+  GVS_HIP(h, hipEventRecord(p.d2h[b], p.copy_out));
+  return GVS_OK;
+}
+
+// The double-buffered cycle under gvs_process_batches and the wire form: k
+// batches from host memory, batch t+1's columns staged and copied in, and
+// batch t-1's copied out, while batch t runs.  A column in pinned caller
+// memory (gvs_host_alloc) is copied to or from directly; any other goes
+// through its slot's pinned staging buffer.  Batches apply in order; the error
+// word is not reset between them, so the batches enqueued behind a failing
+// one do nothing.  The first batch that fails (refused by check_epoch, not
+// wholly enqueued, or a non-zero error word) ends the call: the host state
+// goes back to that batch, the batches before it are collected and count in
+// *applied, the streams are drained, and every output column is zeroed from
+// that batch on (a pinned one may have received stale device data).
+static int pipe_run(gvs_handle* h, std::vector<Column> cols, const uint32_t* counts, uint32_t k,
+                    uint64_t total, const PipeEnqueue& enqueue, uint32_t* applied) {
+  HostPipe& p = h->pipe;
+  if (int r = reset_errors(h)) return r;
+  for (Column& c : cols) c.direct = is_pinned(c.user);
+  HostState snap[2];
+  uint64_t off[2] = {0, 0};
+  uint64_t next_off = 0;  // the first request not enqueued; after a failure, not applied
+  uint32_t enq = 0;       // batches enqueued
+  int stop = GVS_OK;
+  for (uint32_t t = 0;; ++t) {
+    const uint32_t b = t & 1u;
+    if (t < k && stop == GVS_OK) {  // enqueue batch t in slot b
+      snap[b] = save_state(h);
+      off[b] = next_off;
+      stop = check_epoch(h);
+      if (!stop) stop = pipe_enqueue(h, cols, b, t >= 2, next_off, counts[t], enqueue);
+      if (stop) {
+        restore_state(h, snap[b]);
+      } else {
+        advance(h);  // as if applied; rolled back below if it was not
+        next_off += counts[t];
+        enq = t + 1;
+      }
+    }
+    if (t >= 1 && t - 1 < enq) {  // collect batch t-1
+      const uint32_t pb = b ^ 1u;
+      GVS_HIP(h, hipEventSynchronize(p.d2h[pb]));
+      if (const uint32_t e = p.herr[pb]) {  // batch t, if enqueued, did nothing
+        restore_state(h, snap[pb]);
+        stop = decode_error(h, e);
+        next_off = off[pb];
+        break;
+      }
+      for (const Column& c : cols)
+        if (c.out && !c.direct) par_memcpy(c.at(off[pb]), c.buf->pin[pb], counts[t - 1] * c.stride);
+      if (applied) *applied = t;
+    }
+    if (enq <= t) break;
+  }
+  if (stop == GVS_OK) return GVS_OK;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  GVS_HIP(h, hipStreamSynchronize(p.copy));
+  GVS_HIP(h, hipStreamSynchronize(p.copy_out));
+  for (const Column& c : cols)
+    if (c.out) std::memset(c.at(next_off), 0, (size_t)(total - next_off) * c.stride);
+  return stop;
+}
+
 int gvs_process_batches(gvs_handle* h, const gvs_request* reqs, const uint32_t* counts,
                         uint32_t k, gvs_response* out, uint32_t* applied) {
-  if (applied) *applied = 0;
-  if (!h || h->kind != 0 || (k && (!counts || !reqs || !out))) return GVS_ERR_INVALID_ARG;
-  for (uint32_t t = 0; t < k; ++t)
-    if (counts[t] > max_submit(h)) return GVS_ERR_INVALID_ARG;
-  if (h->poisoned) return GVS_ERR_INTEGRITY;
+  uint64_t total;
+  if (int r = batches_begin(h, !k || (reqs && out), counts, k, applied, &total)) return r;
   if (k == 0) return GVS_OK;
   GVS_HIP(h, hipSetDevice(h->device));
   if (int r = pipe_init(h)) return r;
   HostPipe& p = h->pipe;
-  hipStream_t s = h->stream;
-  if (int r = reset_errors(h)) return r;
-  // Caller buffers in pinned memory (gvs_host_alloc) are copied to and from
-  // directly; pageable ones go through the pinned staging pair.
-  const bool pin_in = is_pinned(reqs), pin_out = is_pinned(out);
-  HostState snap[2];
-  uint64_t off[2] = {0, 0};
-  uint64_t next_off = 0;
-  uint32_t enq = 0;  // batches enqueued
-  int stop = GVS_OK;
-  for (uint32_t t = 0;; ++t) {
-    bool more = t < k && stop == GVS_OK;
-    if (more)
-      if (int r = check_epoch(h)) {
-        stop = r;
-        more = false;
-      }
-    if (more) {  // enqueue batch t in slot b
-      const uint32_t b = t & 1u, n = counts[t];
-      const void* src = reqs + next_off;
-      if (!pin_in) {
-        if (t >= 2) GVS_HIP(h, hipEventSynchronize(p.h2d[b]));  // hin[b] free again
-        par_memcpy(p.hin[b], reqs + next_off, (size_t)n * sizeof(gvs_request));
-        src = p.hin[b];
-      }
-      if (t >= 2) GVS_HIP(h, hipStreamWaitEvent(p.copy, p.done[b], 0));  // din[b] consumed
-      if (n)
-        GVS_HIP(h, hipMemcpyAsync(p.din[b], src, (size_t)n * sizeof(gvs_request),
-                                  hipMemcpyHostToDevice, p.copy));
-      GVS_HIP(h, hipEventRecord(p.h2d[b], p.copy));
-      GVS_HIP(h, hipStreamWaitEvent(s, p.h2d[b], 0));
-      if (t >= 2) GVS_HIP(h, hipStreamWaitEvent(s, p.d2h[b], 0));  // dout[b] copied out
-      snap[b] = save_state(h);
-      int rr = run_batch(h, p.din[b], n, p.dout[b], false);
-      if (!rr && h->mode != kSingle) rr = agree_errors(h);
-      if (rr) {  // batch t was not (wholly) enqueued: the ones before it are still collected
-        restore_state(h, snap[b]);
-        stop = rr;
-        more = false;
-      }
-    }
-    if (more) {
-      const uint32_t b = t & 1u, n = counts[t];
-      GVS_HIP(h, hipMemcpyAsync(&p.herr[b], &h->eng[0].scal->error, sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, s));
-      GVS_HIP(h, hipEventRecord(p.done[b], s));
-      GVS_HIP(h, hipStreamWaitEvent(p.copy_out, p.done[b], 0));
-      if (n)
-        GVS_HIP(h, hipMemcpyAsync(pin_out ? (void*)(out + next_off) : (void*)p.hout[b], p.dout[b],
-                                  (size_t)n * sizeof(gvs_response), hipMemcpyDeviceToHost, p.copy_out));
-      GVS_HIP(h, hipEventRecord(p.d2h[b], p.copy_out));
-      advance(h);  // as if applied; rolled back below if it was not
-      off[b] = next_off;
-      next_off += n;
-      enq = t + 1;
-    }
-    if (t >= 1 && t - 1 < enq) {  // collect batch t-1
-      const uint32_t pb = (t - 1) & 1u;
-      GVS_HIP(h, hipEventSynchronize(p.d2h[pb]));
-      if (const uint32_t e = p.herr[pb]) {
-        restore_state(h, snap[pb]);
-        GVS_HIP(h, hipStreamSynchronize(s));  // batch t, if enqueued, did nothing
-        GVS_HIP(h, hipStreamSynchronize(p.copy));
-        GVS_HIP(h, hipStreamSynchronize(p.copy_out));
-        // the batches from the failed one on were not applied: their range of
-        // `out` (which a pinned caller buffer may have received stale device
-        // responses into) is zeroed, never left holding other batches' data
-        uint64_t total = 0;
-        for (uint32_t i = 0; i < k; ++i) total += counts[i];
-        std::memset(out + off[pb], 0, (size_t)(total - off[pb]) * sizeof(gvs_response));
-        return decode_error(h, e);
-      }
-      if (!pin_out)
-        par_memcpy(out + off[pb], p.hout[pb], (size_t)counts[t - 1] * sizeof(gvs_response));
-      if (applied) *applied = t;
-    }
-    if (!more && t >= enq) break;
-  }
-  if (stop != GVS_OK) {  // the batches not applied answer nothing
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < k; ++i) total += counts[i];
-    GVS_HIP(h, hipStreamSynchronize(p.copy_out));
-    std::memset(out + next_off, 0, (size_t)(total - next_off) * sizeof(gvs_response));
-  }
-  return stop;
+  return pipe_run(h, {col_in(reqs, sizeof(gvs_request), p.in), col_out(out, sizeof(gvs_response), p.out)},
+                  counts, k, total,
+                  [&](uint32_t b, uint32_t n) {
+                    return run_batch(h, (const uint4*)p.in.dev[b], n, (uint4*)p.out.dev[b], false);
+                  },
+                  applied);
+}
+
+// the responses from request `off` on answer nothing: batches not applied
+static int zero_responses_device(gvs_handle* h, uint4* out, uint64_t off, uint64_t total) {
+  if (off >= total) return GVS_OK;
+  GVS_HIP(h, hipMemsetAsync(out + off * kAbiU4, 0, (size_t)(total - off) * sizeof(gvs_response), h->stream));
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return GVS_OK;
 }
 
 int gvs_process_batches_device(gvs_handle* h, const void* d_reqs, const uint32_t* counts, uint32_t k,
                                void* d_out, uint32_t* applied) {
-  if (applied) *applied = 0;
-  if (!h || h->kind != 0 || (k && (!counts || !d_reqs || !d_out))) return GVS_ERR_INVALID_ARG;
-  for (uint32_t t = 0; t < k; ++t)
-    if (counts[t] > max_submit(h)) return GVS_ERR_INVALID_ARG;
-  if (h->poisoned) return GVS_ERR_INTEGRITY;
+  uint64_t total;
+  if (int r = batches_begin(h, !k || (d_reqs && d_out), counts, k, applied, &total)) return r;
   if (k == 0) return GVS_OK;
   GVS_HIP(h, hipSetDevice(h->device));
   HostPipe& p = h->pipe;  // pinned error words, one per batch
@@ -2185,8 +2281,7 @@ int gvs_process_batches_device(gvs_handle* h, const void* d_reqs, const uint32_t
   const uint4* in = (const uint4*)d_reqs;
   uint4* out = (uint4*)d_out;
   std::vector<HostState> snap(k);
-  uint64_t off = 0, total = 0;
-  for (uint32_t t = 0; t < k; ++t) total += counts[t];
+  uint64_t off = 0;
   uint32_t enq = 0;
   int stop = GVS_OK;
   // every batch enqueued back to back; the error word is not reset between
@@ -2250,18 +2345,14 @@ int gvs_process_batches_device(gvs_handle* h, const void* d_reqs, const uint32_t
   for (uint32_t t = 0; t < enq; ++t) {
     if (const uint32_t e = p.errs[t]) {
       restore_state(h, snap[t]);
-      GVS_HIP(h, hipMemsetAsync(out + off * kAbiU4, 0, (size_t)(total - off) * sizeof(gvs_response),
-                                h->stream));
-      GVS_HIP(h, hipStreamSynchronize(h->stream));
+      if (int r = zero_responses_device(h, out, off, total)) return r;
       return decode_error(h, e);
     }
     off += counts[t];
     if (applied) *applied = t + 1;
   }
-  if (stop != GVS_OK && off < total) {  // the batches not applied answer nothing
-    GVS_HIP(h, hipMemsetAsync(out + off * kAbiU4, 0, (size_t)(total - off) * sizeof(gvs_response), h->stream));
-    GVS_HIP(h, hipStreamSynchronize(h->stream));
-  }
+  if (stop != GVS_OK)  // the batches not applied answer nothing
+    if (int r = zero_responses_device(h, out, off, total)) return r;
   return stop;
 }
 
@@ -2308,10 +2399,9 @@ int gvs_wire_decode_device(gvs_handle* h, const void* d_wire, uint32_t stride,
       (n && (!d_wire || !d_lens || !d_times || !d_reqs)))
     return GVS_ERR_INVALID_ARG;
   GVS_HIP(h, hipSetDevice(h->device));
-  enqueue_wire_decode(h, d_wire, stride, d_lens, n, d_times, d_reqs, d_sigs, d_status);
-  GVS_HIP(h, hipGetLastError());
-  GVS_HIP(h, hipStreamSynchronize(h->stream));
-  return GVS_OK;
+  return launch_sync(h, nullptr, [&] {
+    enqueue_wire_decode(h, d_wire, stride, d_lens, n, d_times, d_reqs, d_sigs, d_status);
+  });
 }
 
 int gvs_wire_encode_device(gvs_handle* h, const void* d_resps, uint32_t n, void* d_wire,
@@ -2319,10 +2409,7 @@ int gvs_wire_encode_device(gvs_handle* h, const void* d_resps, uint32_t n, void*
   if (!h || stride < kWireResp || stride > kWireSlotMax || (n && (!d_resps || !d_wire || !d_lens)))
     return GVS_ERR_INVALID_ARG;
   GVS_HIP(h, hipSetDevice(h->device));
-  enqueue_wire_encode(h, d_resps, n, d_wire, stride, d_lens);
-  GVS_HIP(h, hipGetLastError());
-  GVS_HIP(h, hipStreamSynchronize(h->stream));
-  return GVS_OK;
+  return launch_sync(h, nullptr, [&] { enqueue_wire_encode(h, d_resps, n, d_wire, stride, d_lens); });
 }
 
 // grapevine's challenge signing context (types/src/lib.rs:13)
@@ -2410,33 +2497,16 @@ static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const
   uint32_t* status = d_status ? d_status : h->wire.status;
   enqueue_wire_decode(h, d_in, in_stride, d_in_lens, n, d_times, h->in_stage, sigs, status);
   mark(h, "wire_decode");
+  const uint8_t* pk = (const uint8_t*)h->in_stage + 16;  // gvs_request.auth_identity
   if (d_chal && h->ed_auth) {  // pure Ed25519 over the 32 challenge bytes, no context
     sr::EdArgs a{};
-    a.pk = (const uint8_t*)h->in_stage + 16;  // gvs_request.auth_identity
-    a.pk_stride = sizeof(gvs_request);
-    a.msg = (const uint8_t*)d_chal;
-    a.msg_stride = 32;
-    a.msg_len = 32;
-    a.sig = (const uint8_t*)sigs;
-    a.sig_stride = 64;
-    a.n = n;
-    a.reqs = h->in_stage;
-    a.status = status;
+    verify_fields(a, pk, sizeof(gvs_request), d_chal, 32, 32, sigs, 64, n, nullptr, h->in_stage, status);
     enqueue_ed_verify(h, a);
     mark(h, "ed_verify");
   } else if (d_chal) {
     sr::SrArgs a;
     (void)sr_args((const uint8_t*)kChallengeContext, sizeof kChallengeContext - 1, a);
-    a.pk = (const uint8_t*)h->in_stage + 16;  // gvs_request.auth_identity
-    a.pk_stride = sizeof(gvs_request);
-    a.msg = (const uint8_t*)d_chal;
-    a.msg_stride = 32;
-    a.msg_len = 32;
-    a.sig = (const uint8_t*)sigs;
-    a.sig_stride = 64;
-    a.n = n;
-    a.reqs = h->in_stage;
-    a.status = status;
+    verify_fields(a, pk, sizeof(gvs_request), d_chal, 32, 32, sigs, 64, n, nullptr, h->in_stage, status);
     enqueue_sr_verify(h, a);
     mark(h, "sr_verify");
   }
@@ -2527,14 +2597,14 @@ static int wire_batch_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
   WireStage& w = h->wire;
   if (int r = bounce_begin(h)) return r;
   if (n) {
-    if (int r = h2d(h, 0, w.in, in, (size_t)n * in_stride)) return r;
-    if (int r = h2d(h, 1, w.in_lens, in_lens, (size_t)n * 4)) return r;
-    if (int r = h2d(h, 2, w.times, times, (size_t)n * 8)) return r;
+    if (int r = h2d(h, w.in, in, (size_t)n * in_stride)) return r;
+    if (int r = h2d(h, w.in_lens, in_lens, (size_t)n * 4)) return r;
+    if (int r = h2d(h, w.times, times, (size_t)n * 8)) return r;
     if (ci.challenges)
-      if (int r = h2d(h, 3, w.chal, ci.challenges, (size_t)n * 32)) return r;
+      if (int r = h2d(h, w.chal, ci.challenges, (size_t)n * 32)) return r;
     if (ci.seeded()) {
-      if (int r = h2d(h, 3, w.seeds, ci.seeds, (size_t)n * 32)) return r;
-      if (int r = h2d(h, 8, w.draws, ci.draws, (size_t)n * 8)) return r;
+      if (int r = h2d(h, w.seeds, ci.seeds, (size_t)n * 32)) return r;
+      if (int r = h2d(h, w.draws, ci.draws, (size_t)n * 8)) return r;
     }
   }
   ChalSrc cs;
@@ -2545,14 +2615,14 @@ static int wire_batch_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
                          w.out_lens, w.sigs, w.status))
     return r;
   if (n) {
-    if (int r = d2h(h, 4, out, w.out, (size_t)n * out_stride)) return r;
-    if (int r = d2h(h, 5, out_lens, w.out_lens, (size_t)n * 4)) return r;
+    if (int r = d2h(h, out, w.out, (size_t)n * out_stride)) return r;
+    if (int r = d2h(h, out_lens, w.out_lens, (size_t)n * 4)) return r;
     if (sigs)
-      if (int r = d2h(h, 6, sigs, w.sigs, (size_t)n * 64)) return r;
+      if (int r = d2h(h, sigs, w.sigs, (size_t)n * 64)) return r;
     if (decode_status)
-      if (int r = d2h(h, 7, decode_status, w.status, (size_t)n * 4)) return r;
+      if (int r = d2h(h, decode_status, w.status, (size_t)n * 4)) return r;
     if (ci.seeded() && ci.challenges_out)
-      if (int r = d2h(h, 9, ci.challenges_out, w.chal, (size_t)n * 32)) return r;
+      if (int r = d2h(h, ci.challenges_out, w.chal, (size_t)n * 32)) return r;
   }
   return bounce_done(h, finish(h));
 }
@@ -2584,13 +2654,9 @@ static int wire_pipe_seeded_init(gvs_handle* h) {
   WirePipe& p = h->wpipe;
   if (p.seeded) return GVS_OK;
   const uint64_t cap = max_submit(h);
-  for (int b = 0; b < 2; ++b) {
-    if (int rc = dalloc_t(h, &p.dseed[b], cap * 2)) return rc;
-    if (int rc = dalloc_t(h, &p.ddraw[b], cap)) return rc;
-    GVS_HIP(h, hipHostMalloc((void**)&p.hseed[b], cap * 32, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.hdraw[b], cap * 8, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.hchout[b], cap * 32, hipHostMallocDefault));
-  }
+  if (int rc = pipe_buf(h, p.seed, cap * 32)) return rc;
+  if (int rc = pipe_buf(h, p.draw, cap * 8)) return rc;
+  if (int rc = pipe_buf(h, p.chout, cap * 32, &p.chal)) return rc;
   p.seeded = true;
   return GVS_OK;
 }
@@ -2598,157 +2664,59 @@ static int wire_pipe_seeded_init(gvs_handle* h) {
 static int wire_pipe_init(gvs_handle* h) {
   WirePipe& p = h->wpipe;
   if (p.ready) return GVS_OK;
-  if (int r = pipe_init(h)) return r;  // the copy streams and the host pipeline's pinned words
+  if (int r = pipe_init(h)) return r;  // the copy streams, the events and the pinned error words
   const uint64_t cap = max_submit(h), big = cap * kWireSlotMax;
-  for (int b = 0; b < 2; ++b) {
-    if (int rc = dalloc_t(h, &p.din[b], big)) return rc;
-    if (int rc = dalloc_t(h, &p.dout[b], big)) return rc;
-    if (int rc = dalloc_t(h, &p.dlens[b], cap)) return rc;
-    if (int rc = dalloc_t(h, &p.dolens[b], cap)) return rc;
-    if (int rc = dalloc_t(h, &p.dstat[b], cap)) return rc;
-    if (int rc = dalloc_t(h, &p.dtimes[b], cap)) return rc;
-    if (int rc = dalloc_t(h, &p.dchal[b], cap * 2)) return rc;
-    GVS_HIP(h, hipHostMalloc((void**)&p.hin[b], big, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.hout[b], big, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.hchal[b], cap * 32, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.hlens[b], cap * 4, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.holens[b], cap * 4, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.hstat[b], cap * 4, hipHostMallocDefault));
-    GVS_HIP(h, hipHostMalloc((void**)&p.htimes[b], cap * 8, hipHostMallocDefault));
-    GVS_HIP(h, hipEventCreateWithFlags(&p.h2d[b], hipEventDisableTiming));
-    GVS_HIP(h, hipEventCreateWithFlags(&p.done[b], hipEventDisableTiming));
-    GVS_HIP(h, hipEventCreateWithFlags(&p.d2h[b], hipEventDisableTiming));
-  }
+  if (int rc = pipe_buf(h, p.in, big)) return rc;
+  if (int rc = pipe_buf(h, p.out, big)) return rc;
+  if (int rc = pipe_buf(h, p.lens, cap * 4)) return rc;
+  if (int rc = pipe_buf(h, p.olens, cap * 4)) return rc;
+  if (int rc = pipe_buf(h, p.stat, cap * 4)) return rc;
+  if (int rc = pipe_buf(h, p.times, cap * 8)) return rc;
+  if (int rc = pipe_buf(h, p.chal, cap * 32)) return rc;
   p.ready = true;
   return GVS_OK;
 }
 
-// k wire batches from host memory, double-buffered like gvs_process_batches:
-// batch t+1's messages go up on the copy stream and batch t-1's results come
-// down on the other while batch t runs (decode, challenge check, the store,
-// encode).  At the first batch that fails, its error is returned and it and
-// the later batches are not applied.  (gvs_process_wire_batches and its seeded
-// form.)
+// k wire batches from host memory through pipe_run: batch t+1's messages go
+// up and batch t-1's results come down while batch t runs (decode, challenge
+// check, the store, encode).  (gvs_process_wire_batches and its seeded form.)
 static int wire_batches_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
                              const uint32_t* in_lens, const uint32_t* counts, uint32_t k,
                              const uint64_t* times, const ChalIn& ci, uint8_t* out,
                              uint32_t out_stride, uint32_t* out_lens, uint32_t* decode_status,
                              uint32_t* applied) {
-  if (applied) *applied = 0;
-  if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) ||
-      (k && (!counts || !in || !in_lens || !times || !out || !out_lens)) || !ci.ok())
-    return GVS_ERR_INVALID_ARG;
-  const uint8_t* challenges = (const uint8_t*)ci.challenges;
-  const uint8_t* seeds = (const uint8_t*)ci.seeds;
-  uint8_t* chal_out = ci.seeded() ? (uint8_t*)ci.challenges_out : nullptr;
-  for (uint32_t t = 0; t < k; ++t)
-    if (counts[t] > max_submit(h)) return GVS_ERR_INVALID_ARG;
-  if (h->poisoned) return GVS_ERR_INTEGRITY;
+  uint64_t total;
+  const bool args_ok = wire_strides_ok(in_stride, out_stride) &&
+                       (!k || (in && in_lens && times && out && out_lens)) && ci.ok();
+  if (int r = batches_begin(h, args_ok, counts, k, applied, &total)) return r;
   if (k == 0) return GVS_OK;
   GVS_HIP(h, hipSetDevice(h->device));
   if (int r = wire_pipe_init(h)) return r;
-  if (seeds)
+  if (ci.seeded())
     if (int r = wire_pipe_seeded_init(h)) return r;
   if (int r = wire_stage_init(h, false)) return r;
   WirePipe& p = h->wpipe;
-  HostPipe& hp = h->pipe;
-  hipStream_t s = h->stream;
-  if (int r = reset_errors(h)) return r;
-  // message and response slabs in pinned memory (gvs_host_alloc) are copied
-  // to and from directly; pageable ones go through the pinned staging pair
-  const bool pin_in = is_pinned(in), pin_out = is_pinned(out);
-  HostState snap[2];
-  uint64_t off[2] = {0, 0}, next_off = 0;
-  uint32_t enq = 0;
-  int stop = GVS_OK;
-  for (uint32_t t = 0;; ++t) {
-    bool more = t < k && stop == GVS_OK;
-    if (more)
-      if (int r = check_epoch(h)) {
-        stop = r;
-        more = false;
-      }
-    if (more) {  // enqueue batch t in slot b
-      const uint32_t b = t & 1u, n = counts[t];
-      if (t >= 2) GVS_HIP(h, hipEventSynchronize(p.h2d[b]));  // staging b free again
-      const uint8_t* src = pin_in ? in + next_off * in_stride : p.hin[b];
-      if (!pin_in) par_memcpy(p.hin[b], in + next_off * in_stride, (size_t)n * in_stride);
-      std::memcpy(p.hlens[b], in_lens + next_off, (size_t)n * 4);
-      std::memcpy(p.htimes[b], times + next_off, (size_t)n * 8);
-      if (challenges) std::memcpy(p.hchal[b], challenges + next_off * 32, (size_t)n * 32);
-      if (seeds) {
-        std::memcpy(p.hseed[b], seeds + next_off * 32, (size_t)n * 32);
-        std::memcpy(p.hdraw[b], ci.draws + next_off, (size_t)n * 8);
-      }
-      if (t >= 2) GVS_HIP(h, hipStreamWaitEvent(hp.copy, p.done[b], 0));  // device slot b consumed
-      if (n) {
-        GVS_HIP(h, hipMemcpyAsync(p.din[b], src, (size_t)n * in_stride, hipMemcpyHostToDevice, hp.copy));
-        GVS_HIP(h, hipMemcpyAsync(p.dlens[b], p.hlens[b], (size_t)n * 4, hipMemcpyHostToDevice, hp.copy));
-        GVS_HIP(h, hipMemcpyAsync(p.dtimes[b], p.htimes[b], (size_t)n * 8, hipMemcpyHostToDevice, hp.copy));
-        if (challenges)
-          GVS_HIP(h, hipMemcpyAsync(p.dchal[b], p.hchal[b], (size_t)n * 32, hipMemcpyHostToDevice, hp.copy));
-        if (seeds) {
-          GVS_HIP(h, hipMemcpyAsync(p.dseed[b], p.hseed[b], (size_t)n * 32, hipMemcpyHostToDevice, hp.copy));
-          GVS_HIP(h, hipMemcpyAsync(p.ddraw[b], p.hdraw[b], (size_t)n * 8, hipMemcpyHostToDevice, hp.copy));
-        }
-      }
-      GVS_HIP(h, hipEventRecord(p.h2d[b], hp.copy));
-      GVS_HIP(h, hipStreamWaitEvent(s, p.h2d[b], 0));
-      if (t >= 2) GVS_HIP(h, hipStreamWaitEvent(s, p.d2h[b], 0));  // results b copied out
-      snap[b] = save_state(h);
-      ChalSrc cs;
-      if (challenges) cs.chal = p.dchal[b];
-      if (seeds) cs = ChalSrc{p.dchal[b], p.dseed[b], p.ddraw[b]};
-      if (int r = wire_batch(h, p.din[b], in_stride, p.dlens[b], n, p.dtimes[b], cs, p.dout[b],
-                             out_stride, p.dolens[b], nullptr, p.dstat[b]))
-        return r;
-      if (h->mode != kSingle)
-        if (int r = agree_errors(h)) return r;
-      GVS_HIP(h, hipMemcpyAsync(&hp.herr[b], &h->eng[0].scal->error, sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, s));
-      GVS_HIP(h, hipEventRecord(p.done[b], s));
-      GVS_HIP(h, hipStreamWaitEvent(hp.copy_out, p.done[b], 0));
-      if (n) {
-        GVS_HIP(h, hipMemcpyAsync(pin_out ? out + next_off * out_stride : p.hout[b], p.dout[b],
-                                  (size_t)n * out_stride, hipMemcpyDeviceToHost, hp.copy_out));
-        GVS_HIP(h, hipMemcpyAsync(p.holens[b], p.dolens[b], (size_t)n * 4, hipMemcpyDeviceToHost, hp.copy_out));
-        GVS_HIP(h, hipMemcpyAsync(p.hstat[b], p.dstat[b], (size_t)n * 4, hipMemcpyDeviceToHost, hp.copy_out));
-        if (chal_out)
-          GVS_HIP(h, hipMemcpyAsync(p.hchout[b], p.dchal[b], (size_t)n * 32, hipMemcpyDeviceToHost, hp.copy_out));
-      }
-      GVS_HIP(h, hipEventRecord(p.d2h[b], hp.copy_out));
-      advance(h);  // as if applied; rolled back below if it was not
-      off[b] = next_off;
-      next_off += n;
-      enq = t + 1;
-    }
-    if (t >= 1 && t - 1 < enq) {  // collect batch t-1
-      const uint32_t pb = (t - 1) & 1u, n = counts[t - 1];
-      GVS_HIP(h, hipEventSynchronize(p.d2h[pb]));
-      if (const uint32_t e = hp.herr[pb]) {
-        restore_state(h, snap[pb]);
-        GVS_HIP(h, hipStreamSynchronize(s));
-        GVS_HIP(h, hipStreamSynchronize(hp.copy));
-        GVS_HIP(h, hipStreamSynchronize(hp.copy_out));
-        // unapplied batches: zero their range of `out` and their lengths (a
-        // pinned `out` may have received stale device responses)
-        uint64_t total = 0;
-        for (uint32_t i = 0; i < k; ++i) total += counts[i];
-        std::memset(out + off[pb] * out_stride, 0, (size_t)(total - off[pb]) * out_stride);
-        std::memset(out_lens + off[pb], 0, (size_t)(total - off[pb]) * 4);
-        if (decode_status) std::memset(decode_status + off[pb], 0, (size_t)(total - off[pb]) * 4);
-        if (chal_out) std::memset(chal_out + off[pb] * 32, 0, (size_t)(total - off[pb]) * 32);
-        return decode_error(h, e);
-      }
-      if (!pin_out) par_memcpy(out + off[pb] * out_stride, p.hout[pb], (size_t)n * out_stride);
-      std::memcpy(out_lens + off[pb], p.holens[pb], (size_t)n * 4);
-      if (decode_status) std::memcpy(decode_status + off[pb], p.hstat[pb], (size_t)n * 4);
-      if (chal_out) std::memcpy(chal_out + off[pb] * 32, p.hchout[pb], (size_t)n * 32);
-      if (applied) *applied = t;
-    }
-    if (!more && t >= enq) break;
+  std::vector<Column> cols = {col_in(in, in_stride, p.in), col_in(in_lens, 4, p.lens),
+                              col_in(times, 8, p.times)};
+  if (ci.challenges) cols.push_back(col_in(ci.challenges, 32, p.chal));
+  if (ci.seeded()) {
+    cols.push_back(col_in(ci.seeds, 32, p.seed));
+    cols.push_back(col_in(ci.draws, 8, p.draw));
   }
-  return stop;
+  cols.push_back(col_out(out, out_stride, p.out));
+  cols.push_back(col_out(out_lens, 4, p.olens));
+  if (decode_status) cols.push_back(col_out(decode_status, 4, p.stat));
+  if (ci.seeded() && ci.challenges_out) cols.push_back(col_out(ci.challenges_out, 32, p.chout));
+  return pipe_run(h, std::move(cols), counts, k, total,
+                  [&](uint32_t b, uint32_t n) {
+                    ChalSrc cs;
+                    if (ci.challenges) cs.chal = p.chal.dev[b];
+                    if (ci.seeded()) cs = ChalSrc{p.chal.dev[b], p.seed.dev[b], (const uint64_t*)p.draw.dev[b]};
+                    return wire_batch(h, p.in.dev[b], in_stride, (const uint32_t*)p.lens.dev[b], n,
+                                      (const uint64_t*)p.times.dev[b], cs, p.out.dev[b], out_stride,
+                                      (uint32_t*)p.olens.dev[b], nullptr, (uint32_t*)p.stat.dev[b]);
+                  },
+                  applied);
 }
 
 int gvs_process_wire_batches(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
@@ -2783,12 +2751,19 @@ int gvs_challenge_derive_device(gvs_handle* h, const void* d_seeds, const uint64
   if (!h || (n && (!d_seeds || !d_draws || !d_out)) || !aligned16(d_seeds) || !aligned16(d_out))
     return GVS_ERR_INVALID_ARG;
   GVS_HIP(h, hipSetDevice(h->device));
-  h->n_marks = 0;
-  mark(h, "start");
-  enqueue_challenge(h, d_seeds, d_draws, n, d_out);
-  mark(h, "challenge");
-  GVS_HIP(h, hipGetLastError());
-  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return launch_sync(h, "challenge", [&] { enqueue_challenge(h, d_seeds, d_draws, n, d_out); });
+}
+
+// Device staging of the stand-alone host calls (gvs_challenge_derive, the two
+// verify calls), grow-only: a hipMalloc / hipFree per call would change the
+// page tables (and invalidate the TLB) between batches.
+static int dev_scratch(gvs_handle* h, size_t bytes) {
+  if (h->sr_cap >= bytes) return GVS_OK;
+  if (h->sr_dev) GVS_HIP(h, hipFree(h->sr_dev));
+  h->sr_dev = nullptr;
+  h->sr_cap = 0;
+  GVS_HIP(h, hipMalloc((void**)&h->sr_dev, bytes));
+  h->sr_cap = bytes;
   return GVS_OK;
 }
 
@@ -2798,24 +2773,23 @@ int gvs_challenge_derive(gvs_handle* h, const uint8_t* seeds, const uint64_t* dr
   if (!n) return GVS_OK;
   GVS_HIP(h, hipSetDevice(h->device));
   const size_t b_seed = (size_t)n * 32, b_draw = (size_t)n * 8;
-  const size_t need = 2 * b_seed + b_draw;
-  // the grow-only device staging of gvs_sr25519_verify
-  if (h->sr_cap < need) {
-    if (h->sr_dev) GVS_HIP(h, hipFree(h->sr_dev));
-    h->sr_dev = nullptr;
-    h->sr_cap = 0;
-    GVS_HIP(h, hipMalloc((void**)&h->sr_dev, need));
-    h->sr_cap = need;
-  }
+  if (int r = dev_scratch(h, 2 * b_seed + b_draw)) return r;
   uint8_t* d = h->sr_dev;  // seeds | out | draws: every part 16-byte aligned
   if (int r = bounce_begin(h)) return r;
-  if (int r = h2d(h, 0, d, seeds, b_seed)) return r;
-  if (int r = h2d(h, 1, d + 2 * b_seed, draws, b_draw)) return r;
+  if (int r = h2d(h, d, seeds, b_seed)) return r;
+  if (int r = h2d(h, d + 2 * b_seed, draws, b_draw)) return r;
   if (int r = gvs_challenge_derive_device(h, d, (const uint64_t*)(d + 2 * b_seed), n, d + b_seed))
     return bounce_done(h, r);
-  if (int r = d2h(h, 4, out, d + b_seed, b_seed)) return r;
+  if (int r = d2h(h, out, d + b_seed, b_seed)) return r;
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   return bounce_done(h, GVS_OK);
+}
+
+static bool verify_device_args_ok(gvs_handle* h, const void* d_pks, uint32_t pk_stride, const void* d_msgs,
+                                  uint32_t msg_stride, uint32_t msg_len, const void* d_sigs,
+                                  uint32_t sig_stride, uint32_t n, const uint32_t* d_ok) {
+  return h && pk_stride >= 32 && sig_stride >= 64 && msg_stride >= msg_len && msg_len <= 4096 &&
+         (!n || (d_pks && (!msg_len || d_msgs) && d_sigs && d_ok));
 }
 
 int gvs_sr25519_verify_device(gvs_handle* h, const void* d_pks, uint32_t pk_stride,
@@ -2823,116 +2797,68 @@ int gvs_sr25519_verify_device(gvs_handle* h, const void* d_pks, uint32_t pk_stri
                               const void* d_sigs, uint32_t sig_stride, uint32_t n,
                               const uint8_t* context, uint32_t context_len, uint32_t* d_ok) {
   sr::SrArgs a;
-  if (!h || sr_args(context, context_len, a) || pk_stride < 32 || sig_stride < 64 ||
-      msg_stride < msg_len || msg_len > 4096 || (n && (!d_pks || (msg_len && !d_msgs) || !d_sigs || !d_ok)))
+  if (!h || sr_args(context, context_len, a) ||
+      !verify_device_args_ok(h, d_pks, pk_stride, d_msgs, msg_stride, msg_len, d_sigs, sig_stride, n, d_ok))
     return GVS_ERR_INVALID_ARG;
   GVS_HIP(h, hipSetDevice(h->device));
-  a.pk = (const uint8_t*)d_pks;
-  a.pk_stride = pk_stride;
-  a.msg = (const uint8_t*)d_msgs;
-  a.msg_stride = msg_stride;
-  a.msg_len = msg_len;
-  a.sig = (const uint8_t*)d_sigs;
-  a.sig_stride = sig_stride;
-  a.n = n;
-  a.ok = d_ok;
-  h->n_marks = 0;
-  mark(h, "start");
-  enqueue_sr_verify(h, a);
-  mark(h, "sr_verify");
-  GVS_HIP(h, hipGetLastError());
-  GVS_HIP(h, hipStreamSynchronize(h->stream));
-  return GVS_OK;
-}
-
-int gvs_sr25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, uint32_t msg_len,
-                       const uint8_t* sigs, uint32_t n, const uint8_t* context,
-                       uint32_t context_len, uint32_t* ok) {
-  if (!h || (n && (!pks || (msg_len && !msgs) || !sigs || !ok)) || msg_len > 4096)
-    return GVS_ERR_INVALID_ARG;
-  if (!n) return GVS_OK;
-  GVS_HIP(h, hipSetDevice(h->device));
-  const size_t b_pk = (size_t)n * 32, b_msg = (size_t)n * msg_len, b_sig = (size_t)n * 64,
-               b_ok = (size_t)n * 4;
-  const size_t need = b_pk + b_msg + b_sig + b_ok + 64;
-  // grow-only device staging: a hipMalloc / hipFree per call would change the
-  // page tables (and invalidate the TLB) between batches
-  if (h->sr_cap < need) {
-    if (h->sr_dev) GVS_HIP(h, hipFree(h->sr_dev));
-    h->sr_dev = nullptr;
-    h->sr_cap = 0;
-    GVS_HIP(h, hipMalloc((void**)&h->sr_dev, need));
-    h->sr_cap = need;
-  }
-  uint8_t* d = h->sr_dev;
-  if (int r = bounce_begin(h)) return r;
-  if (int r = h2d(h, 0, d, pks, b_pk)) return r;
-  if (int r = h2d(h, 1, d + b_pk, msgs, b_msg)) return r;
-  if (int r = h2d(h, 2, d + b_pk + b_msg, sigs, b_sig)) return r;
-  uint32_t* d_ok = (uint32_t*)(d + ((b_pk + b_msg + b_sig + 3) & ~(size_t)3));
-  if (int r = gvs_sr25519_verify_device(h, d, 32, d + b_pk, msg_len ? msg_len : 1, msg_len,
-                                        d + b_pk + b_msg, 64, n, context, context_len, d_ok))
-    return bounce_done(h, r);
-  if (int r = d2h(h, 4, ok, d_ok, b_ok)) return r;
-  GVS_HIP(h, hipStreamSynchronize(h->stream));
-  return bounce_done(h, GVS_OK);
+  verify_fields(a, d_pks, pk_stride, d_msgs, msg_stride, msg_len, d_sigs, sig_stride, n, d_ok, nullptr, nullptr);
+  return launch_sync(h, "sr_verify", [&] { enqueue_sr_verify(h, a); });
 }
 
 int gvs_ed25519_verify_device(gvs_handle* h, const void* d_pks, uint32_t pk_stride,
                               const void* d_msgs, uint32_t msg_stride, uint32_t msg_len,
                               const void* d_sigs, uint32_t sig_stride, uint32_t n, uint32_t* d_ok) {
-  if (!h || pk_stride < 32 || sig_stride < 64 || msg_stride < msg_len || msg_len > 4096 ||
-      (n && (!d_pks || (msg_len && !d_msgs) || !d_sigs || !d_ok)))
+  if (!verify_device_args_ok(h, d_pks, pk_stride, d_msgs, msg_stride, msg_len, d_sigs, sig_stride, n, d_ok))
     return GVS_ERR_INVALID_ARG;
   GVS_HIP(h, hipSetDevice(h->device));
   sr::EdArgs a{};
-  a.pk = (const uint8_t*)d_pks;
-  a.pk_stride = pk_stride;
-  a.msg = (const uint8_t*)d_msgs;
-  a.msg_stride = msg_stride;
-  a.msg_len = msg_len;
-  a.sig = (const uint8_t*)d_sigs;
-  a.sig_stride = sig_stride;
-  a.n = n;
-  a.ok = d_ok;
-  h->n_marks = 0;
-  mark(h, "start");
-  enqueue_ed_verify(h, a);
-  mark(h, "ed_verify");
-  GVS_HIP(h, hipGetLastError());
-  GVS_HIP(h, hipStreamSynchronize(h->stream));
-  return GVS_OK;
+  verify_fields(a, d_pks, pk_stride, d_msgs, msg_stride, msg_len, d_sigs, sig_stride, n, d_ok, nullptr, nullptr);
+  return launch_sync(h, "ed_verify", [&] { enqueue_ed_verify(h, a); });
 }
 
-int gvs_ed25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, uint32_t msg_len,
-                       const uint8_t* sigs, uint32_t n, uint32_t* ok) {
+// gvs_sr25519_verify and gvs_ed25519_verify: n keys, messages and signatures
+// from host memory through the device scratch, the verdicts back.  `verify`
+// is the scheme's device call on packed arrays (strides 32, msg_len, 64).
+using VerifyDevice = std::function<int(const uint8_t* d_pks, const uint8_t* d_msgs, const uint8_t* d_sigs,
+                                       uint32_t* d_ok)>;
+static int verify_host(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, uint32_t msg_len,
+                       const uint8_t* sigs, uint32_t n, uint32_t* ok, const VerifyDevice& verify) {
   if (!h || (n && (!pks || (msg_len && !msgs) || !sigs || !ok)) || msg_len > 4096)
     return GVS_ERR_INVALID_ARG;
   if (!n) return GVS_OK;
   GVS_HIP(h, hipSetDevice(h->device));
   const size_t b_pk = (size_t)n * 32, b_msg = (size_t)n * msg_len, b_sig = (size_t)n * 64,
                b_ok = (size_t)n * 4;
-  const size_t need = b_pk + b_msg + b_sig + b_ok + 64;
-  // the grow-only device staging of gvs_sr25519_verify
-  if (h->sr_cap < need) {
-    if (h->sr_dev) GVS_HIP(h, hipFree(h->sr_dev));
-    h->sr_dev = nullptr;
-    h->sr_cap = 0;
-    GVS_HIP(h, hipMalloc((void**)&h->sr_dev, need));
-    h->sr_cap = need;
-  }
+  if (int r = dev_scratch(h, b_pk + b_msg + b_sig + b_ok + 64)) return r;
   uint8_t* d = h->sr_dev;
   if (int r = bounce_begin(h)) return r;
-  if (int r = h2d(h, 0, d, pks, b_pk)) return r;
-  if (int r = h2d(h, 1, d + b_pk, msgs, b_msg)) return r;
-  if (int r = h2d(h, 2, d + b_pk + b_msg, sigs, b_sig)) return r;
+  if (int r = h2d(h, d, pks, b_pk)) return r;
+  if (int r = h2d(h, d + b_pk, msgs, b_msg)) return r;
+  if (int r = h2d(h, d + b_pk + b_msg, sigs, b_sig)) return r;
   uint32_t* d_ok = (uint32_t*)(d + ((b_pk + b_msg + b_sig + 3) & ~(size_t)3));
-  if (int r = gvs_ed25519_verify_device(h, d, 32, d + b_pk, msg_len ? msg_len : 1, msg_len,
-                                        d + b_pk + b_msg, 64, n, d_ok))
-    return bounce_done(h, r);
-  if (int r = d2h(h, 4, ok, d_ok, b_ok)) return r;
+  if (int r = verify(d, d + b_pk, d + b_pk + b_msg, d_ok)) return bounce_done(h, r);
+  if (int r = d2h(h, ok, d_ok, b_ok)) return r;
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   return bounce_done(h, GVS_OK);
+}
+
+int gvs_sr25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, uint32_t msg_len,
+                       const uint8_t* sigs, uint32_t n, const uint8_t* context,
+                       uint32_t context_len, uint32_t* ok) {
+  return verify_host(h, pks, msgs, msg_len, sigs, n, ok,
+                     [&](const uint8_t* d_pks, const uint8_t* d_msgs, const uint8_t* d_sigs, uint32_t* d_ok) {
+                       return gvs_sr25519_verify_device(h, d_pks, 32, d_msgs, msg_len ? msg_len : 1, msg_len,
+                                                        d_sigs, 64, n, context, context_len, d_ok);
+                     });
+}
+
+int gvs_ed25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, uint32_t msg_len,
+                       const uint8_t* sigs, uint32_t n, uint32_t* ok) {
+  return verify_host(h, pks, msgs, msg_len, sigs, n, ok,
+                     [&](const uint8_t* d_pks, const uint8_t* d_msgs, const uint8_t* d_sigs, uint32_t* d_ok) {
+                       return gvs_ed25519_verify_device(h, d_pks, 32, d_msgs, msg_len ? msg_len : 1, msg_len,
+                                                        d_sigs, 64, n, d_ok);
+                     });
 }
 
 int gvs_set_expiry_cutoff(gvs_handle* h, uint64_t cutoff) {
@@ -3394,9 +3320,9 @@ int gvs_oram_access_batch(gvs_oram* o, const gvs_block_op* ops, uint32_t n, uint
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
   if (int r = bounce_begin(h)) return r;
-  if (int r = h2d(h, 0, h->in_stage, ops, (size_t)n * sizeof(gvs_block_op))) return r;
+  if (int r = h2d(h, h->in_stage, ops, (size_t)n * sizeof(gvs_block_op))) return r;
   if (int r = oram_batch(h, h->eng[0], h->in_stage, n, h->out_stage)) return r;
-  if (int r = d2h(h, 4, out, h->out_stage, (size_t)n * 1024)) return r;
+  if (int r = d2h(h, out, h->out_stage, (size_t)n * 1024)) return r;
   return bounce_done(h, finish(h));
 }
 
@@ -3450,9 +3376,9 @@ int gvs_omap_access_batch(gvs_omap* o, const gvs_omap_op* ops, uint32_t n, gvs_o
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
   if (int r = bounce_begin(h)) return r;
-  if (int r = h2d(h, 0, h->in_stage, ops, (size_t)n * sizeof(gvs_omap_op))) return r;
+  if (int r = h2d(h, h->in_stage, ops, (size_t)n * sizeof(gvs_omap_op))) return r;
   if (int r = omap_batch(h, h->eng[0], h->in_stage, n, h->out_stage)) return r;
-  if (int r = d2h(h, 4, out, h->out_stage, (size_t)n * sizeof(gvs_omap_result))) return r;
+  if (int r = d2h(h, out, h->out_stage, (size_t)n * sizeof(gvs_omap_result))) return r;
   return bounce_done(h, finish(h));
 }
 
