@@ -14,8 +14,9 @@ HDRS := $(wildcard grapevine_amd/csrc/*.h) include/gvstore.h include/gvstore_tes
 SRHOST := tests/libsrhost.so
 EDHOST := tests/libedhost.so
 CHACHAHOST := tests/libchachahost.so
+AEADHOST := tests/libaeadhost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -37,11 +38,16 @@ $(EDHOST): tests/ed_host.cpp grapevine_amd/csrc/gvs_ed25519.h grapevine_amd/csrc
 $(CHACHAHOST): tests/chacha_host.cpp grapevine_amd/csrc/gvs_chacha.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/chacha_host.cpp
 
+# the device channel cipher's primitives (AES-256, GF(2^128), the serial
+# AES-256-GCM) built for the CPU (tests/test_aead.py)
+$(AEADHOST): tests/aead_host.cpp grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/aead_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

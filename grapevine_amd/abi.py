@@ -94,6 +94,15 @@ class GvsStats(ctypes.Structure):
 # wire codec (gvs_process_wire_batch, include/gvstore.h)
 WIRE_REQUEST_BYTES, WIRE_RESPONSE_BYTES, WIRE_SLOT_MAX = 1099, 1042, 2048
 WIRE_OK, WIRE_DECODE_ERROR, WIRE_BAD_FIELD, WIRE_BAD_SIGNATURE = 0, 1, 2, 3
+WIRE_BAD_CHANNEL_TAG = 4  # GVS_WIRE_BAD_CHANNEL_TAG: the request's channel tag does not verify
+# the channel cipher (gvs_aead_open / gvs_aead_seal: AES-256-GCM)
+AEAD_KEY_BYTES, AEAD_IV_BYTES, AEAD_TAG_BYTES, AEAD_AAD_MAX, AEAD_TEXT_MAX = 32, 12, 16, 64, WIRE_SLOT_MAX
+
+
+def noise_iv(counter):
+    """Noise's AESGCM nonce for message number `counter` of a cipher state:
+    four zero bytes, then the counter as 64 bits big-endian."""
+    return bytes(4) + int(counter).to_bytes(8, "big")
 
 COMM_ID_BYTES = 128
 # GVS_FLAG_AUTH_STORAGE: AES-CTR sealed tables; rows of tables 0, 1, 2 and

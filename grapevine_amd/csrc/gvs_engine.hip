@@ -34,6 +34,7 @@
 #include "gvs_sr25519.h"
 #include "gvs_ed25519.h"
 #include "gvs_chacha.h"
+#include "gvs_aead.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
 #ifndef GVS_MA_EXTRA_LDS
@@ -251,6 +252,16 @@ struct WireStage {
   uint4* chal = nullptr;     // n x 32-B challenges (given, or derived from seeds and draws)
   uint4* seeds = nullptr;    // seeded calls: n x 32-B channel seeds
   uint64_t* draws = nullptr; // seeded calls: n draw indices
+  // channel calls (gvs_process_wire_batch_channel[_device]): the opened
+  // requests and the encoded responses between the cipher and the codec,
+  // their lengths and the open verdicts; the host form's keys and IVs
+  uint8_t* pt_in = nullptr;
+  uint8_t* pt_out = nullptr;
+  uint32_t* pt_lens = nullptr;
+  uint32_t* enc_lens = nullptr;
+  uint32_t* opened = nullptr;
+  uint4* ckeys[2] = {};      // open, seal: n x 32 B
+  uint32_t* civs[2] = {};    // open, seal: n x 12 B
 };
 
 // Double-buffered wire path (gvs_process_wire_batches): one batch's wire
@@ -276,7 +287,7 @@ struct WirePipe {
 // (DESIGN.md §3 "Counters").  Pageable caller memory is therefore copied by
 // the host into grow-only pinned buffers and moved by DMA from there.
 struct Bounce {
-  static constexpr int kSlots = 10;  // the seeded wire batch: 5 in, 5 out
+  static constexpr int kSlots = 14;  // the channel wire batch: 9 in, 5 out
   void* buf[kSlots] = {};
   size_t cap[kSlots] = {};
   int used = 0;  // slots taken by this call's copies, in order (bounce_begin: 0)
@@ -2447,7 +2458,7 @@ static void enqueue_challenge(gvs_handle* h, const void* d_seeds, const uint64_t
 // may not pass them), the host-side slabs only for gvs_process_wire_batch, the
 // seeds and draw indices only for the seeded host call (the seeded device call
 // needs the challenge staging alone).
-static int wire_stage_init(gvs_handle* h, bool io, bool seeded = false) {
+static int wire_stage_init(gvs_handle* h, bool io, bool seeded = false, bool channel = false) {
   WireStage& w = h->wire;
   const uint64_t cap = max_submit(h);
   if (!w.sigs) {
@@ -2467,6 +2478,18 @@ static int wire_stage_init(gvs_handle* h, bool io, bool seeded = false) {
     if (int rc = dalloc_t(h, &w.seeds, cap * 2)) return rc;
     if (int rc = dalloc_t(h, &w.draws, cap)) return rc;
   }
+  if (channel && !w.pt_in) {
+    if (int rc = dalloc_t(h, &w.pt_in, cap * kWireSlotMax)) return rc;
+    if (int rc = dalloc_t(h, &w.pt_out, cap * kWireSlotMax)) return rc;
+    if (int rc = dalloc_t(h, &w.pt_lens, cap)) return rc;
+    if (int rc = dalloc_t(h, &w.enc_lens, cap)) return rc;
+    if (int rc = dalloc_t(h, &w.opened, cap)) return rc;
+  }
+  if (channel && io && !w.ckeys[0])
+    for (int k = 0; k < 2; ++k) {
+      if (int rc = dalloc_t(h, &w.ckeys[k], cap * 2)) return rc;
+      if (int rc = dalloc_t(h, &w.civs[k], cap * 3)) return rc;
+    }
   return GVS_OK;
 }
 
@@ -2479,15 +2502,69 @@ struct ChalSrc {
   const uint64_t* draws = nullptr;
 };
 
+// The channel calls' ciphers (gvs_aead.h), per request: the connection's
+// receive cipher opens the request, its send cipher seals the response.
+// Keys n x 32 B, IVs n x 12 B; device pointers inside wire_batch.
+struct ChanKeys {
+  const void* open_keys = nullptr;
+  const void* open_ivs = nullptr;
+  const void* seal_keys = nullptr;
+  const void* seal_ivs = nullptr;
+  bool all() const { return open_keys && open_ivs && seal_keys && seal_ivs; }
+};
+
+// the AES table on the device, for handles without authenticated storage too
+static int aead_init(gvs_handle* h) {
+  if (h->te) return GVS_OK;
+  uint8_t sb[256];
+  uint32_t te0[256];
+  aes_sbox(sb);
+  aes_tables(sb, te0);
+  uint32_t* te = nullptr;
+  if (int rc = dalloc_t(h, &te, 256)) return rc;
+  GVS_HIP(h, hipMemcpy(te, te0, sizeof te0, hipMemcpyHostToDevice));
+  h->te = te;
+  return GVS_OK;
+}
+
+static void enqueue_aead(gvs_handle* h, bool seal, AeadArgs a) {
+  if (!a.n) return;
+  a.te = h->te;
+  const dim3 grid((a.n + kAeadMsgs - 1) / kAeadMsgs), block(64 * kAeadMsgs);
+  if (seal)
+    hipLaunchKernelGGL(k_aead<true>, grid, block, 0, h->stream, a);
+  else
+    hipLaunchKernelGGL(k_aead<false>, grid, block, 0, h->stream, a);
+}
+
 // decode -> (challenge check) -> the batch -> encode, all on the engine
 // stream; the request and response slabs live in the handle's host-API
 // staging.
 static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const uint32_t* d_in_lens,
                       uint32_t n, const uint64_t* d_times, const ChalSrc& cs, void* d_out,
-                      uint32_t out_stride, uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status) {
-  if (int rc = wire_stage_init(h, false)) return rc;
+                      uint32_t out_stride, uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status,
+                      const ChanKeys* ch = nullptr) {
+  if (int rc = wire_stage_init(h, false, false, ch != nullptr)) return rc;
   h->n_marks = 0;
   mark(h, "start");
+  WireStage& w = h->wire;
+  if (ch) {  // the requests' plaintext (length 0 where the tag fails) is what the decoder reads
+    AeadArgs a{};
+    a.keys = (const uint4*)ch->open_keys;
+    a.ivs = (const uint32_t*)ch->open_ivs;
+    a.in = (const uint8_t*)d_in;
+    a.in_stride = in_stride;
+    a.in_lens = d_in_lens;
+    a.n = n;
+    a.out = w.pt_in;
+    a.out_stride = in_stride;
+    a.out_lens = w.pt_lens;
+    a.ok = w.opened;
+    enqueue_aead(h, false, a);
+    mark(h, "aead_open");
+    d_in = w.pt_in;
+    d_in_lens = w.pt_lens;
+  }
   const void* d_chal = cs.chal;
   if (cs.seeds) {
     enqueue_challenge(h, cs.seeds, cs.draws, n, cs.chal);
@@ -2511,8 +2588,25 @@ static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const
     mark(h, "sr_verify");
   }
   if (int r = run_batch_body(h, h->in_stage, n, h->out_stage)) return r;
-  enqueue_wire_encode(h, h->out_stage, n, d_out, out_stride, d_out_lens);
+  enqueue_wire_encode(h, h->out_stage, n, ch ? w.pt_out : d_out, out_stride, ch ? w.enc_lens : d_out_lens);
   mark(h, "wire_encode");
+  if (ch) {  // seal what was encoded; an unopened request's status and empty answer are merged here
+    AeadArgs a{};
+    a.keys = (const uint4*)ch->seal_keys;
+    a.ivs = (const uint32_t*)ch->seal_ivs;
+    a.in = w.pt_out;
+    a.in_stride = out_stride;
+    a.in_lens = w.enc_lens;
+    a.n = n;
+    a.out = (uint8_t*)d_out;
+    a.out_stride = out_stride;
+    a.out_lens = d_out_lens;
+    a.opened = w.opened;
+    a.status = status;
+    a.bad_status = GVS_WIRE_BAD_CHANNEL_TAG;
+    enqueue_aead(h, true, a);
+    mark(h, "aead_seal");
+  }
   GVS_HIP(h, hipGetLastError());
   return GVS_OK;
 }
@@ -2531,18 +2625,30 @@ struct ChalIn {
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// the channel calls: slots are whole cipher blocks, and a sealed response fits
+static bool channel_strides_ok(uint32_t in_stride, uint32_t out_stride) {
+  return in_stride % 16 == 0 && out_stride % 16 == 0 && out_stride >= kWireResp + kAeadTag;
+}
+
 // gvs_process_wire_batch_device and its seeded form
 static int wire_batch_device(gvs_handle* h, const void* d_in, uint32_t in_stride,
                              const uint32_t* d_in_lens, uint32_t n, const uint64_t* d_times,
                              const ChalIn& ci, void* d_out, uint32_t out_stride,
-                             uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status) {
+                             uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status,
+                             const ChanKeys* ch = nullptr) {
   if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) || n > max_submit(h) ||
       (n && (!d_in || !d_in_lens || !d_times || !d_out || !d_out_lens)) || !ci.ok() ||
       !aligned16(ci.seeds) || !aligned16(ci.challenges_out))
     return GVS_ERR_INVALID_ARG;
+  if (ch && (!channel_strides_ok(in_stride, out_stride) || (n && !ch->all()) || !aligned16(d_in) ||
+             !aligned16(d_out) || !aligned16(ch->open_keys) || !aligned16(ch->seal_keys) ||
+             ((uintptr_t)ch->open_ivs & 3u) || ((uintptr_t)ch->seal_ivs & 3u)))
+    return GVS_ERR_INVALID_ARG;
   if (h->poisoned) return GVS_ERR_INTEGRITY;
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
+  if (ch)
+    if (int r = aead_init(h)) return r;
   ChalSrc cs{const_cast<void*>(ci.challenges), nullptr, nullptr};
   if (ci.seeded()) {
     if (int rc = wire_stage_init(h, false, true)) return rc;
@@ -2550,7 +2656,7 @@ static int wire_batch_device(gvs_handle* h, const void* d_in, uint32_t in_stride
   }
   if (int r = reset_errors(h)) return r;
   if (int r = wire_batch(h, d_in, in_stride, d_in_lens, n, d_times, cs, d_out, out_stride,
-                         d_out_lens, d_sigs, d_status))
+                         d_out_lens, d_sigs, d_status, ch))
     return r;
   if (n && ci.seeded() && ci.challenges_out)
     GVS_HIP(h, hipMemcpyAsync(ci.challenges_out, cs.chal, (size_t)n * 32, hipMemcpyDeviceToDevice,
@@ -2586,16 +2692,27 @@ int gvs_process_wire_batch_seeded_device(gvs_handle* h, const void* d_in, uint32
 static int wire_batch_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
                            const uint32_t* in_lens, uint32_t n, const uint64_t* times,
                            const ChalIn& ci, uint8_t* out, uint32_t out_stride, uint32_t* out_lens,
-                           uint8_t* sigs, uint32_t* decode_status) {
+                           uint8_t* sigs, uint32_t* decode_status, const ChanKeys* ch = nullptr) {
   if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) || n > max_submit(h) ||
-      (n && (!in || !in_lens || !times || !out || !out_lens)) || !ci.ok())
+      (n && (!in || !in_lens || !times || !out || !out_lens)) || !ci.ok() ||
+      (ch && (!channel_strides_ok(in_stride, out_stride) || (n && !ch->all()))))
     return GVS_ERR_INVALID_ARG;
   if (h->poisoned) return GVS_ERR_INTEGRITY;
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
-  if (int rc = wire_stage_init(h, true, ci.seeded())) return rc;
+  if (ch)
+    if (int r = aead_init(h)) return r;
+  if (int rc = wire_stage_init(h, true, ci.seeded(), ch != nullptr)) return rc;
   WireStage& w = h->wire;
   if (int r = bounce_begin(h)) return r;
+  ChanKeys dch;  // the ciphers' keys and IVs on the device
+  if (ch) dch = ChanKeys{w.ckeys[0], w.civs[0], w.ckeys[1], w.civs[1]};
+  if (n && ch) {
+    if (int r = h2d(h, w.ckeys[0], ch->open_keys, (size_t)n * 32)) return r;
+    if (int r = h2d(h, w.civs[0], ch->open_ivs, (size_t)n * kAeadIv)) return r;
+    if (int r = h2d(h, w.ckeys[1], ch->seal_keys, (size_t)n * 32)) return r;
+    if (int r = h2d(h, w.civs[1], ch->seal_ivs, (size_t)n * kAeadIv)) return r;
+  }
   if (n) {
     if (int r = h2d(h, w.in, in, (size_t)n * in_stride)) return r;
     if (int r = h2d(h, w.in_lens, in_lens, (size_t)n * 4)) return r;
@@ -2612,7 +2729,7 @@ static int wire_batch_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
   if (ci.seeded()) cs = ChalSrc{w.chal, w.seeds, w.draws};
   if (int r = reset_errors(h)) return r;
   if (int r = wire_batch(h, w.in, in_stride, w.in_lens, n, w.times, cs, w.out, out_stride,
-                         w.out_lens, w.sigs, w.status))
+                         w.out_lens, w.sigs, w.status, ch ? &dch : nullptr))
     return r;
   if (n) {
     if (int r = d2h(h, out, w.out, (size_t)n * out_stride)) return r;
@@ -2648,6 +2765,39 @@ int gvs_process_wire_batch_seeded(gvs_handle* h, const uint8_t* in, uint32_t in_
   ci.challenges_out = challenges_out;
   return wire_batch_host(h, in, in_stride, in_lens, n, times, ci, out, out_stride, out_lens, sigs,
                          decode_status);
+}
+
+int gvs_process_wire_batch_channel(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
+                                   const uint32_t* in_lens, uint32_t n, const uint64_t* times,
+                                   const uint8_t* seeds, const uint64_t* draws,
+                                   const uint8_t* open_keys, const uint8_t* open_ivs,
+                                   const uint8_t* seal_keys, const uint8_t* seal_ivs, uint8_t* out,
+                                   uint32_t out_stride, uint32_t* out_lens, uint8_t* sigs,
+                                   uint32_t* decode_status, uint8_t* challenges_out) {
+  ChalIn ci;
+  ci.seeds = seeds;
+  ci.draws = draws;
+  ci.challenges_out = challenges_out;
+  const ChanKeys ch{open_keys, open_ivs, seal_keys, seal_ivs};
+  return wire_batch_host(h, in, in_stride, in_lens, n, times, ci, out, out_stride, out_lens, sigs,
+                         decode_status, &ch);
+}
+
+int gvs_process_wire_batch_channel_device(gvs_handle* h, const void* d_in, uint32_t in_stride,
+                                          const uint32_t* d_in_lens, uint32_t n,
+                                          const uint64_t* d_times, const void* d_seeds,
+                                          const uint64_t* d_draws, const void* d_open_keys,
+                                          const void* d_open_ivs, const void* d_seal_keys,
+                                          const void* d_seal_ivs, void* d_out, uint32_t out_stride,
+                                          uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status,
+                                          void* d_challenges_out) {
+  ChalIn ci;
+  ci.seeds = d_seeds;
+  ci.draws = d_draws;
+  ci.challenges_out = d_challenges_out;
+  const ChanKeys ch{d_open_keys, d_open_ivs, d_seal_keys, d_seal_ivs};
+  return wire_batch_device(h, d_in, in_stride, d_in_lens, n, d_times, ci, d_out, out_stride,
+                           d_out_lens, d_sigs, d_status, &ch);
 }
 
 static int wire_pipe_seeded_init(gvs_handle* h) {
@@ -2859,6 +3009,127 @@ int gvs_ed25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, u
                        return gvs_ed25519_verify_device(h, d_pks, 32, d_msgs, msg_len ? msg_len : 1, msg_len,
                                                         d_sigs, 64, n, d_ok);
                      });
+}
+
+// ---------------------------------------------------- channel cipher alone
+
+struct AeadCall {
+  const void* keys;
+  const void* ivs;
+  const void* aad;
+  uint32_t aad_stride;
+  const uint32_t* aad_lens;
+  const void* in;
+  uint32_t in_stride;
+  const uint32_t* in_lens;
+  uint32_t n;
+  void* out;
+  uint32_t out_stride;
+  uint32_t* out_lens;
+  uint32_t* ok;
+};
+
+static bool aead_stride_ok(uint32_t s) { return s >= 16 && s % 16 == 0 && s <= kAeadTextMax + kAeadTag; }
+
+static bool aead_call_ok(gvs_handle* h, const AeadCall& c, bool seal) {
+  return h && c.n <= max_submit(h) && aead_stride_ok(c.in_stride) && aead_stride_ok(c.out_stride) &&
+         (!c.aad || (c.aad_lens && c.aad_stride >= 16 && c.aad_stride % 16 == 0)) &&
+         (!c.n || (c.keys && c.ivs && c.in && c.in_lens && c.out && c.out_lens && (seal || c.ok)));
+}
+
+static int aead_device(gvs_handle* h, const AeadCall& c, bool seal) {
+  if (!aead_call_ok(h, c, seal) || !aligned16(c.keys) || !aligned16(c.aad) || !aligned16(c.in) ||
+      !aligned16(c.out) || ((uintptr_t)c.ivs & 3u))
+    return GVS_ERR_INVALID_ARG;
+  GVS_HIP(h, hipSetDevice(h->device));
+  if (int r = aead_init(h)) return r;
+  AeadArgs a{};
+  a.keys = (const uint4*)c.keys;
+  a.ivs = (const uint32_t*)c.ivs;
+  a.aad = (const uint8_t*)c.aad;
+  a.aad_stride = c.aad_stride;
+  a.aad_lens = c.aad_lens;
+  a.in = (const uint8_t*)c.in;
+  a.in_stride = c.in_stride;
+  a.in_lens = c.in_lens;
+  a.n = c.n;
+  a.out = (uint8_t*)c.out;
+  a.out_stride = c.out_stride;
+  a.out_lens = c.out_lens;
+  a.ok = c.ok;
+  return launch_sync(h, seal ? "aead_seal" : "aead_open", [&] { enqueue_aead(h, seal, a); });
+}
+
+// the host forms: the lengths are checked here (the device forms fail such a
+// message alone), then everything goes through the device scratch
+static int aead_host(gvs_handle* h, const AeadCall& c, bool seal) {
+  if (!aead_call_ok(h, c, seal)) return GVS_ERR_INVALID_ARG;
+  for (uint32_t k = 0; k < c.n; ++k) {
+    const uint32_t len = c.in_lens[k], text = seal ? len : (len < kAeadTag ? 0u : len - kAeadTag);
+    if (len > c.in_stride || text > kAeadTextMax || text + (seal ? kAeadTag : 0u) > c.out_stride ||
+        (c.aad && (c.aad_lens[k] > kAeadAadMax || c.aad_lens[k] > c.aad_stride)))
+      return GVS_ERR_INVALID_ARG;
+  }
+  if (!c.n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const size_t n = c.n, b_key = n * 32, b_iv = (n * kAeadIv + 15) & ~(size_t)15,
+               b_aad = c.aad ? n * c.aad_stride : 0, b_in = n * c.in_stride, b_out = n * c.out_stride,
+               b_u32 = (n * 4 + 15) & ~(size_t)15;
+  if (int r = dev_scratch(h, b_key + b_iv + b_aad + b_in + b_out + 4 * b_u32)) return r;
+  uint8_t* d = h->sr_dev;  // every part 16-byte aligned
+  uint8_t *d_iv = d + b_key, *d_aad = d_iv + b_iv, *d_in = d_aad + b_aad, *d_out = d_in + b_in;
+  uint32_t* d_u32[4];  // aad_lens, in_lens, out_lens, ok
+  for (int k = 0; k < 4; ++k) d_u32[k] = (uint32_t*)(d_out + b_out + k * b_u32);
+  if (int r = bounce_begin(h)) return r;
+  if (int r = h2d(h, d, c.keys, b_key)) return r;
+  if (int r = h2d(h, d_iv, c.ivs, n * kAeadIv)) return r;
+  if (c.aad) {
+    if (int r = h2d(h, d_aad, c.aad, b_aad)) return r;
+    if (int r = h2d(h, d_u32[0], c.aad_lens, n * 4)) return r;
+  }
+  if (int r = h2d(h, d_in, c.in, b_in)) return r;
+  if (int r = h2d(h, d_u32[1], c.in_lens, n * 4)) return r;
+  const AeadCall dc{d, d_iv, c.aad ? d_aad : nullptr, c.aad_stride, d_u32[0], d_in, c.in_stride, d_u32[1],
+                    c.n, d_out, c.out_stride, d_u32[2], d_u32[3]};
+  if (int r = aead_device(h, dc, seal)) return bounce_done(h, r);
+  if (int r = d2h(h, c.out, d_out, b_out)) return r;
+  if (int r = d2h(h, c.out_lens, d_u32[2], n * 4)) return r;
+  if (c.ok)
+    if (int r = d2h(h, c.ok, d_u32[3], n * 4)) return r;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return bounce_done(h, GVS_OK);
+}
+
+int gvs_aead_open_device(gvs_handle* h, const void* d_keys, const void* d_ivs, const void* d_aad,
+                         uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                         uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                         uint32_t out_stride, uint32_t* d_out_lens, uint32_t* d_ok) {
+  return aead_device(h, AeadCall{d_keys, d_ivs, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, d_ok}, false);
+}
+
+int gvs_aead_seal_device(gvs_handle* h, const void* d_keys, const void* d_ivs, const void* d_aad,
+                         uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                         uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                         uint32_t out_stride, uint32_t* d_out_lens) {
+  return aead_device(h, AeadCall{d_keys, d_ivs, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, nullptr}, true);
+}
+
+int gvs_aead_open(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const uint8_t* aad,
+                  uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                  const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                  uint32_t* out_lens, uint32_t* ok) {
+  return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, ok}, false);
+}
+
+int gvs_aead_seal(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const uint8_t* aad,
+                  uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                  const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                  uint32_t* out_lens) {
+  return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, nullptr}, true);
 }
 
 int gvs_set_expiry_cutoff(gvs_handle* h, uint64_t cutoff) {

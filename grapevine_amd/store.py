@@ -37,6 +37,8 @@ EXPORTED = (
     "gvs_ed25519_verify", "gvs_ed25519_verify_device",
     "gvs_challenge_derive", "gvs_challenge_derive_device", "gvs_process_wire_batch_seeded",
     "gvs_process_wire_batch_seeded_device", "gvs_process_wire_batches_seeded",
+    "gvs_aead_open", "gvs_aead_open_device", "gvs_aead_seal", "gvs_aead_seal_device",
+    "gvs_process_wire_batch_channel", "gvs_process_wire_batch_channel_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -82,6 +84,13 @@ def load_library(path=None):
                                                     vp, ctypes.POINTER(u32)]
     lib.gvs_process_wire_batch_seeded_device.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, vp, u32, vp, vp,
                                                          vp, vp]
+    lib.gvs_process_wire_batch_channel.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32,
+                                                   vp, vp, vp, vp]
+    lib.gvs_process_wire_batch_channel_device.argtypes = lib.gvs_process_wire_batch_channel.argtypes
+    lib.gvs_aead_open.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, vp]
+    lib.gvs_aead_open_device.argtypes = lib.gvs_aead_open.argtypes
+    lib.gvs_aead_seal.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp]
+    lib.gvs_aead_seal_device.argtypes = lib.gvs_aead_seal.argtypes
     lib.gvs_challenge_derive.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_challenge_derive_device.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_sr25519_verify.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp]
@@ -399,6 +408,74 @@ class ObliviousStore:
             o += int(c)
         return res
 
+    def process_wire_batch_channel(self, msgs, times, seeds, draws, open_keys, open_ivs, seal_keys,
+                                   seal_ivs, in_stride=None, out_stride=None):
+        """process_wire_batch_seeded behind the channel cipher
+        (gvs_process_wire_batch_channel): msgs are the requests as ciphertext
+        | tag under open_keys[k] (n, 32) / open_ivs[k] (n, 12, `abi.noise_iv`),
+        and the responses come back as ciphertext | tag under seal_keys[k] /
+        seal_ivs[k].  A request whose tag fails answers b"" with status
+        WIRE_BAD_CHANNEL_TAG.  -> what process_wire_batch_seeded returns."""
+        if in_stride is None:
+            in_stride = -(-max([len(m) for m in msgs] + [1]) // 16) * 16
+        if out_stride is None:
+            out_stride = -(-(abi.WIRE_RESPONSE_BYTES + abi.AEAD_TAG_BYTES) // 16) * 16
+        slab, lens, stride = self._wire_slab(msgs, in_stride)
+        n = len(lens)
+        times = np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.uint64), (n,)))
+        out = np.zeros((n, out_stride), np.uint8)
+        out_lens = np.zeros(n, np.uint32)
+        sigs = np.zeros((n, 64), np.uint8)
+        status = np.zeros(n, np.uint32)
+        chal = np.zeros((n, 32), np.uint8)
+        seeds, draws = self._seeds_draws(seeds, draws, n)
+        keys = [np.ascontiguousarray(a, np.uint8).reshape(n, w)
+                for a, w in ((open_keys, 32), (open_ivs, 12), (seal_keys, 32), (seal_ivs, 12))]
+        self._check(self.lib.gvs_process_wire_batch_channel(
+            self.h, slab.ctypes.data, stride, lens.ctypes.data, n, times.ctypes.data,
+            seeds.ctypes.data if seeds is not None else None,
+            draws.ctypes.data if draws is not None else None, *[a.ctypes.data for a in keys],
+            out.ctypes.data, out_stride, out_lens.ctypes.data, sigs.ctypes.data, status.ctypes.data,
+            chal.ctypes.data))
+        return [out[k, :out_lens[k]].tobytes() for k in range(n)], sigs, status, chal
+
+    def _aead(self, seal, keys, ivs, msgs, aads):
+        n = len(msgs)
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(n, 32)
+        ivs = np.ascontiguousarray(ivs, np.uint8).reshape(n, 12)
+        pad16 = lambda v: -(-max(v, 1) // 16) * 16
+        slab, lens, stride = self._wire_slab(msgs, pad16(max([len(m) for m in msgs] + [0])))
+        aad = aad_lens = None
+        aad_stride = 16
+        if aads is not None:
+            aad, aad_lens, aad_stride = self._wire_slab(aads, pad16(max([len(a) for a in aads] + [0])))
+        out_stride = stride + 16 if seal else stride
+        out = np.zeros((n, out_stride), np.uint8)
+        out_lens = np.zeros(n, np.uint32)
+        ok = np.ones(n, np.uint32)
+        fn = self.lib.gvs_aead_seal if seal else self.lib.gvs_aead_open
+        self._check(fn(self.h, keys.ctypes.data, ivs.ctypes.data,
+                       aad.ctypes.data if aad is not None else None, aad_stride,
+                       aad_lens.ctypes.data if aad is not None else None, slab.ctypes.data, stride,
+                       lens.ctypes.data, n, out.ctypes.data, out_stride, out_lens.ctypes.data,
+                       *([] if seal else [ok.ctypes.data])))
+        return out, out_lens, ok.astype(bool)
+
+    def aead_seal(self, keys, ivs, msgs, aads=None):
+        """Batched AES-256-GCM sealing on the device (gvs_aead_seal): keys
+        (n, 32) and ivs (n, 12) uint8, msgs a list of n plaintexts, aads an
+        optional list of n byte strings -> list of ciphertext | tag."""
+        out, out_lens, _ = self._aead(True, keys, ivs, msgs, aads)
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))]
+
+    def aead_open(self, keys, ivs, msgs, aads=None):
+        """Batched AES-256-GCM opening on the device (gvs_aead_open): msgs a
+        list of n ciphertext | tag -> (list of plaintexts, (n,) bool verdicts,
+        the (n, stride) output slab); a message that does not verify is b""
+        and its slot all zero."""
+        out, out_lens, ok = self._aead(False, keys, ivs, msgs, aads)
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))], ok, out
+
     def challenge_derive(self, seeds, draws):
         """The challenge stream on the device (gvs_challenge_derive): seeds
         (n, 32) uint8, draws (n,) uint64 -> (n, 32) uint8, row k = draw number
@@ -502,9 +579,9 @@ class ObliviousStore:
         self._check(self.lib.gvs_set_timing(self.h, 1 if on else 0))
 
     def last_timings(self):
-        names = (ctypes.c_char_p * 16)()
-        ms = (ctypes.c_float * 16)()
-        c = self.lib.gvs_last_timings(self.h, names, ms, 16)
+        names = (ctypes.c_char_p * 32)()  # a channel wire batch has more than 16 stages
+        ms = (ctypes.c_float * 32)()
+        c = self.lib.gvs_last_timings(self.h, names, ms, 32)
         return {names[i].decode(): float(ms[i]) for i in range(max(c, 0))}
 
 

@@ -340,6 +340,81 @@ int gvs_process_wire_batch_seeded_device(gvs_handle *h, const void *d_in, uint32
                                          const uint64_t *d_draws, void *d_out, uint32_t out_stride,
                                          uint32_t *d_out_lens, void *d_sigs,
                                          uint32_t *d_decode_status, void *d_challenges_out);
+/* The seeded wire batch behind the attested channel's cipher (README.md:177-185
+ * of the reference: every request arrives, and every response leaves, as an
+ * mc-noise ciphertext; Noise's AESGCM is gvs_aead_open / gvs_aead_seal with
+ * the IV 0^32 | be64(counter)).  `in` holds each request as C | tag under
+ * open_keys[k] / open_ivs[k] (the connection's receive cipher, 32 B / 12 B per
+ * request, contiguous), and `out` receives each response as C | tag under
+ * seal_keys[k] / seal_ivs[k] (its send cipher); out_lens count the tag.  The
+ * AAD is empty [D: the snapshot has no attest.proto, so what the reference
+ * binds there is unknown].  Between the two the seeded call runs unchanged on
+ * the plaintext.  A request whose tag fails (or that is shorter than a tag)
+ * keeps its slot, reaches the decoder as an empty message (a no-op for the
+ * store) and ends with out_lens[k] = 0 and decode_status[k] =
+ * GVS_WIRE_BAD_CHANNEL_TAG; a hard error's empty response stays empty and is
+ * not sealed.  Strides are multiples of 16, out_stride at least
+ * GVS_WIRE_RESPONSE_BYTES + GVS_AEAD_TAG_BYTES rounded up; device pointers to
+ * in, out and the keys are 16-byte aligned, to the IVs 4-byte aligned.  seeds
+ * and draws as in the seeded calls (both NULL: no signature check). */
+#define GVS_WIRE_BAD_CHANNEL_TAG 4u /* decode_status: the request's channel tag does not verify */
+int gvs_process_wire_batch_channel(gvs_handle *h, const uint8_t *in, uint32_t in_stride,
+                                   const uint32_t *in_lens, uint32_t n, const uint64_t *times,
+                                   const uint8_t *seeds, const uint64_t *draws,
+                                   const uint8_t *open_keys, const uint8_t *open_ivs,
+                                   const uint8_t *seal_keys, const uint8_t *seal_ivs, uint8_t *out,
+                                   uint32_t out_stride, uint32_t *out_lens, uint8_t *sigs,
+                                   uint32_t *decode_status, uint8_t *challenges_out);
+int gvs_process_wire_batch_channel_device(gvs_handle *h, const void *d_in, uint32_t in_stride,
+                                          const uint32_t *d_in_lens, uint32_t n,
+                                          const uint64_t *d_times, const void *d_seeds,
+                                          const uint64_t *d_draws, const void *d_open_keys,
+                                          const void *d_open_ivs, const void *d_seal_keys,
+                                          const void *d_seal_ivs, void *d_out, uint32_t out_stride,
+                                          uint32_t *d_out_lens, void *d_sigs,
+                                          uint32_t *d_decode_status, void *d_challenges_out);
+
+/* AES-256-GCM (NIST SP 800-38D, 96-bit IV, 128-bit tag), batched, every
+ * message under a key and an IV of its own: keys n x 32 B and ivs n x 12 B
+ * contiguous; message k's AAD (aad_lens[k] <= GVS_AEAD_AAD_MAX bytes) at aad +
+ * k*aad_stride, or aad = NULL for none; its input at in + k*in_stride, its
+ * output slot at out + k*out_stride.  One wavefront per message, the same
+ * instruction stream whatever keys, IVs, text and tags are (loop counts
+ * follow the lengths alone); synchronous on the handle's stream.
+ *   open: in = C | tag of in_lens[k] bytes -> in_lens[k] - 16 bytes of
+ *     plaintext, out_lens[k] and ok[k] = 1.  A message shorter than a tag, or
+ *     whose tag does not verify, does not fail the call: ok[k] = 0,
+ *     out_lens[k] = 0 and a zeroed slot.
+ *   seal: in = the plaintext of in_lens[k] <= GVS_AEAD_TEXT_MAX bytes -> C |
+ *     tag, out_lens[k] = in_lens[k] + 16.
+ * Every output slot is written whole.  Strides are multiples of 16, at most
+ * GVS_AEAD_TEXT_MAX + 16; n at most a batch; n = 0 is a no-op.  Device
+ * pointers to keys, aad, in and out are 16-byte aligned, to ivs 4-byte
+ * aligned.  A length over its maximum, over its stride, or whose output does
+ * not fit out_stride is GVS_ERR_INVALID_ARG in the host forms; the device
+ * forms cannot see the lengths and fail that message alone (length 0, ok 0). */
+#define GVS_AEAD_KEY_BYTES 32
+#define GVS_AEAD_IV_BYTES 12
+#define GVS_AEAD_TAG_BYTES 16
+#define GVS_AEAD_AAD_MAX 64
+#define GVS_AEAD_TEXT_MAX GVS_WIRE_SLOT_MAX
+int gvs_aead_open(gvs_handle *h, const uint8_t *keys, const uint8_t *ivs, const uint8_t *aad,
+                  uint32_t aad_stride, const uint32_t *aad_lens, const uint8_t *in,
+                  uint32_t in_stride, const uint32_t *in_lens, uint32_t n, uint8_t *out,
+                  uint32_t out_stride, uint32_t *out_lens, uint32_t *ok);
+int gvs_aead_open_device(gvs_handle *h, const void *d_keys, const void *d_ivs, const void *d_aad,
+                         uint32_t aad_stride, const uint32_t *d_aad_lens, const void *d_in,
+                         uint32_t in_stride, const uint32_t *d_in_lens, uint32_t n, void *d_out,
+                         uint32_t out_stride, uint32_t *d_out_lens, uint32_t *d_ok);
+int gvs_aead_seal(gvs_handle *h, const uint8_t *keys, const uint8_t *ivs, const uint8_t *aad,
+                  uint32_t aad_stride, const uint32_t *aad_lens, const uint8_t *in,
+                  uint32_t in_stride, const uint32_t *in_lens, uint32_t n, uint8_t *out,
+                  uint32_t out_stride, uint32_t *out_lens);
+int gvs_aead_seal_device(gvs_handle *h, const void *d_keys, const void *d_ivs, const void *d_aad,
+                         uint32_t aad_stride, const uint32_t *d_aad_lens, const void *d_in,
+                         uint32_t in_stride, const uint32_t *d_in_lens, uint32_t n, void *d_out,
+                         uint32_t out_stride, uint32_t *d_out_lens);
+
 /* The challenge stream alone: out[k] (32 B) = draw number draws[k] of
  * ChaCha20Rng(seeds[k]), that is bytes [32*(d&1), 32*(d&1)+32) of ChaCha20
  * block d >> 1 under key seeds[k] (rand_chacha's layout: 64-bit block counter,
