@@ -15,8 +15,9 @@ SRHOST := tests/libsrhost.so
 EDHOST := tests/libedhost.so
 CHACHAHOST := tests/libchachahost.so
 AEADHOST := tests/libaeadhost.so
+XHOST := tests/libxhost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -43,11 +44,16 @@ $(CHACHAHOST): tests/chacha_host.cpp grapevine_amd/csrc/gvs_chacha.h
 $(AEADHOST): tests/aead_host.cpp grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/aead_host.cpp
 
+# the device X25519 quad ladder (four lane states stepped in a loop) and the
+# Noise HKDF built for the CPU (tests/test_x25519.py)
+$(XHOST): tests/x25519_host.cpp grapevine_amd/csrc/gvs_x25519.h grapevine_amd/csrc/gvs_ed25519.h grapevine_amd/csrc/gvs_sr25519.h grapevine_amd/csrc/gvs_device.h
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/x25519_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

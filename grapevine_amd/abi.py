@@ -98,6 +98,10 @@ WIRE_BAD_CHANNEL_TAG = 4  # GVS_WIRE_BAD_CHANNEL_TAG: the request's channel tag 
 # the channel cipher (gvs_aead_open / gvs_aead_seal: AES-256-GCM)
 AEAD_KEY_BYTES, AEAD_IV_BYTES, AEAD_TAG_BYTES, AEAD_AAD_MAX, AEAD_TEXT_MAX = 32, 12, 16, 64, WIRE_SLOT_MAX
 
+# the channel's key agreement (gvs_x25519: scalars, u-coordinates and results;
+# gvs_noise_hkdf: chaining keys and both outputs, ikm of 0 or X25519_BYTES)
+X25519_BYTES, NOISE_HKDF_BYTES = 32, 64
+
 
 def noise_iv(counter):
     """Noise's AESGCM nonce for message number `counter` of a cipher state:

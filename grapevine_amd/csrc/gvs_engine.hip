@@ -33,6 +33,7 @@
 #include "gvs_wire.h"
 #include "gvs_sr25519.h"
 #include "gvs_ed25519.h"
+#include "gvs_x25519.h"
 #include "gvs_chacha.h"
 #include "gvs_aead.h"
 #include "gvs_spass.h"
@@ -2446,6 +2447,18 @@ static void enqueue_ed_verify(gvs_handle* h, const sr::EdArgs& a) {
                      dim3(sr::kSrThreads), 0, h->stream, a);
 }
 
+static void enqueue_x25519(gvs_handle* h, const sr::XArgs& a) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(sr::k_x25519, dim3((a.n + sr::kXItems - 1) / sr::kXItems), dim3(sr::kXThreads), 0,
+                     h->stream, a);
+}
+
+static void enqueue_noise_hkdf(gvs_handle* h, const sr::HkdfArgs& a) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(sr::k_noise_hkdf, dim3((a.n + sr::kSrThreads - 1) / sr::kSrThreads),
+                     dim3(sr::kSrThreads), 0, h->stream, a);
+}
+
 static void enqueue_challenge(gvs_handle* h, const void* d_seeds, const uint64_t* d_draws, uint32_t n,
                               void* d_out) {
   if (!n) return;
@@ -3009,6 +3022,73 @@ int gvs_ed25519_verify(gvs_handle* h, const uint8_t* pks, const uint8_t* msgs, u
                        return gvs_ed25519_verify_device(h, d_pks, 32, d_msgs, msg_len ? msg_len : 1, msg_len,
                                                         d_sigs, 64, n, d_ok);
                      });
+}
+
+// ------------------------------------------- channel key agreement (gvs_x25519.h)
+
+int gvs_x25519_device(gvs_handle* h, const void* d_scalars, uint32_t scalar_stride, const void* d_points,
+                      uint32_t point_stride, uint32_t n, void* d_out, uint32_t out_stride, uint32_t* d_ok) {
+  if (!h || scalar_stride < 32 || (d_points && point_stride < 32) || out_stride < 32 ||
+      (n && (!d_scalars || !d_out)))
+    return GVS_ERR_INVALID_ARG;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const sr::XArgs a{(const uint8_t*)d_scalars, scalar_stride, (const uint8_t*)d_points, point_stride, n,
+                    (uint8_t*)d_out, out_stride, d_ok};
+  return launch_sync(h, "x25519", [&] { enqueue_x25519(h, a); });
+}
+
+int gvs_x25519(gvs_handle* h, const uint8_t* scalars, const uint8_t* points, uint32_t n, uint8_t* out,
+               uint32_t* ok) {
+  if (!h || (n && (!scalars || !out))) return GVS_ERR_INVALID_ARG;
+  if (!n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const size_t b = (size_t)n * 32;  // scalars | points | out | ok
+  if (int r = dev_scratch(h, 3 * b + (size_t)n * 4)) return r;
+  uint8_t* d = h->sr_dev;
+  if (int r = bounce_begin(h)) return r;
+  if (int r = h2d(h, d, scalars, b)) return r;
+  if (points)
+    if (int r = h2d(h, d + b, points, b)) return r;
+  uint32_t* d_ok = (uint32_t*)(d + 3 * b);
+  if (int r = gvs_x25519_device(h, d, 32, points ? d + b : nullptr, 32, n, d + 2 * b, 32, d_ok))
+    return bounce_done(h, r);
+  if (int r = d2h(h, out, d + 2 * b, b)) return r;
+  if (ok)
+    if (int r = d2h(h, ok, d_ok, (size_t)n * 4)) return r;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return bounce_done(h, GVS_OK);
+}
+
+int gvs_noise_hkdf_device(gvs_handle* h, const void* d_cks, uint32_t ck_stride, const void* d_ikm,
+                          uint32_t ikm_stride, uint32_t ikm_len, uint32_t n, void* d_out1, void* d_out2,
+                          uint32_t out_stride) {
+  if (!h || (ikm_len != 0 && ikm_len != 32) || ck_stride < 64 || ikm_stride < ikm_len || out_stride < 64 ||
+      (n && (!d_cks || (ikm_len && !d_ikm) || !d_out1 || !d_out2)))
+    return GVS_ERR_INVALID_ARG;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const sr::HkdfArgs a{(const uint8_t*)d_cks, ck_stride, (const uint8_t*)d_ikm, ikm_stride, ikm_len, n,
+                       (uint8_t*)d_out1, (uint8_t*)d_out2, out_stride};
+  return launch_sync(h, "noise_hkdf", [&] { enqueue_noise_hkdf(h, a); });
+}
+
+int gvs_noise_hkdf(gvs_handle* h, const uint8_t* cks, const uint8_t* ikm, uint32_t ikm_len, uint32_t n,
+                   uint8_t* out1, uint8_t* out2) {
+  if (!h || (ikm_len != 0 && ikm_len != 32) || (n && (!cks || (ikm_len && !ikm) || !out1 || !out2)))
+    return GVS_ERR_INVALID_ARG;
+  if (!n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const size_t b = (size_t)n * 64, b_ikm = (size_t)n * ikm_len;  // cks | out1 | out2 | ikm
+  if (int r = dev_scratch(h, 3 * b + b_ikm)) return r;
+  uint8_t* d = h->sr_dev;
+  if (int r = bounce_begin(h)) return r;
+  if (int r = h2d(h, d, cks, b)) return r;
+  if (int r = h2d(h, d + 3 * b, ikm, b_ikm)) return r;
+  if (int r = gvs_noise_hkdf_device(h, d, 64, d + 3 * b, ikm_len, ikm_len, n, d + b, d + 2 * b, 64))
+    return bounce_done(h, r);
+  if (int r = d2h(h, out1, d + b, b)) return r;
+  if (int r = d2h(h, out2, d + 2 * b, b)) return r;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return bounce_done(h, GVS_OK);
 }
 
 // ---------------------------------------------------- channel cipher alone

@@ -39,6 +39,7 @@ EXPORTED = (
     "gvs_process_wire_batch_seeded_device", "gvs_process_wire_batches_seeded",
     "gvs_aead_open", "gvs_aead_open_device", "gvs_aead_seal", "gvs_aead_seal_device",
     "gvs_process_wire_batch_channel", "gvs_process_wire_batch_channel_device",
+    "gvs_x25519", "gvs_x25519_device", "gvs_noise_hkdf", "gvs_noise_hkdf_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -99,6 +100,10 @@ def load_library(path=None):
     lib.gvs_sr25519_verify_device.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, u32, vp, u32, vp]
     lib.gvs_ed25519_verify.argtypes = [vp, vp, vp, u32, vp, u32, vp]
     lib.gvs_ed25519_verify_device.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, u32, vp]
+    lib.gvs_x25519.argtypes = [vp, vp, vp, u32, vp, vp]
+    lib.gvs_x25519_device.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp]
+    lib.gvs_noise_hkdf.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    lib.gvs_noise_hkdf_device.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, u32]
     lib.gvs_wire_decode_device.argtypes =[vp, vp, u32, vp, u32, vp, vp, vp, vp]
     lib.gvs_wire_encode_device.argtypes = [vp, vp, u32, vp, u32, vp]
     lib.gvs_process_batches.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(u32)]
@@ -526,6 +531,36 @@ class ObliviousStore:
                                                 msgs.shape[1] if msgs.ndim == 2 else 0,
                                                 sigs.ctypes.data, n, ok.ctypes.data))
         return ok.astype(bool)
+
+    def x25519(self, scalars, points=None):
+        """Batched X25519 on the device (gvs_x25519; RFC 7748): scalars (n, 32)
+        uint8, points (n, 32) uint8 or None for the base point -> ((n, 32)
+        uint8 results, (n,) bool: False where the result is all zero)."""
+        scalars = np.ascontiguousarray(scalars, np.uint8).reshape(-1, 32)
+        n = len(scalars)
+        if points is not None:
+            points = np.ascontiguousarray(points, np.uint8).reshape(n, 32)
+        out = np.zeros((n, 32), np.uint8)
+        ok = np.zeros(n, np.uint32)
+        self._check(self.lib.gvs_x25519(self.h, scalars.ctypes.data,
+                                        points.ctypes.data if points is not None else None, n,
+                                        out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def noise_hkdf(self, cks, ikm=None):
+        """Batched Noise HKDF-SHA-512 on the device (gvs_noise_hkdf): cks
+        (n, 64) uint8, ikm (n, 32) uint8 (MixKey of DH outputs) or None
+        (Split) -> two (n, 64) uint8 outputs."""
+        cks = np.ascontiguousarray(cks, np.uint8).reshape(-1, 64)
+        n = len(cks)
+        if ikm is not None:
+            ikm = np.ascontiguousarray(ikm, np.uint8).reshape(n, 32)
+        out1, out2 = np.zeros((n, 64), np.uint8), np.zeros((n, 64), np.uint8)
+        self._check(self.lib.gvs_noise_hkdf(self.h, cks.ctypes.data,
+                                            ikm.ctypes.data if ikm is not None else None,
+                                            32 if ikm is not None else 0, n, out1.ctypes.data,
+                                            out2.ctypes.data))
+        return out1, out2
 
     def access(self, req):
         out = self.process_batch(np.asarray([req], dtype=abi.REQUEST_DTYPE) if not isinstance(req, np.ndarray) else req.reshape(1))

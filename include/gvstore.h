@@ -464,6 +464,41 @@ int gvs_ed25519_verify_device(gvs_handle *h, const void *d_pks, uint32_t pk_stri
                               const void *d_msgs, uint32_t msg_stride, uint32_t msg_len,
                               const void *d_sigs, uint32_t sig_stride, uint32_t n, uint32_t *d_ok);
 
+/* X25519 (RFC 7748 §5), the key agreement of the attested channel's Noise
+ * handshake: out[k] (32 B, canonical, little-endian) = X25519(scalars[k],
+ * points[k]).  The scalar is clamped in the kernel (decodeScalar25519); the
+ * top bit of the u-coordinate is ignored and a non-canonical u (>= p) is
+ * accepted and reduced.  ok[k] = 1 when the result is non-zero, 0 when it is
+ * all zero (a small-order point: x25519-dalek's was_contributory); the call
+ * itself does not fail, and ok may be NULL.  points = NULL is the base point
+ * u = 9 for every item (public keys).  Batched on the handle's device, four
+ * adjacent lanes per multiplication, the same instruction stream whatever
+ * scalars and points are; synchronous on the handle's stream.  Device form:
+ * item k at d_scalars + k*scalar_stride, d_points + k*point_stride and d_out +
+ * k*out_stride (strides >= 32, no alignment asked). */
+int gvs_x25519(gvs_handle *h, const uint8_t *scalars, const uint8_t *points /* NULL: base point */,
+               uint32_t n, uint8_t *out, uint32_t *ok);
+int gvs_x25519_device(gvs_handle *h, const void *d_scalars, uint32_t scalar_stride,
+                      const void *d_points, uint32_t point_stride, uint32_t n,
+                      void *d_out, uint32_t out_stride, uint32_t *d_ok);
+
+/* Noise's HKDF with HMAC-SHA-512, two outputs [D: the suite is
+ * Noise_IX_25519_AESGCM_SHA512]: temp = HMAC(cks[k], ikm[k]), out1[k] =
+ * HMAC(temp, 0x01), out2[k] = HMAC(temp, out1[k] || 0x02); cks, out1 and out2
+ * are 64 B per item.  ikm_len is one value per call: 32 (MixKey of a DH
+ * output: out1 is the next chaining key, the first 32 bytes of out2 the
+ * cipher key) or 0 (Split: the first 32 bytes of out1 and of out2 are the two
+ * directions' gvs_aead_* keys; ikm may be NULL); any other value is
+ * GVS_ERR_INVALID_ARG.  One thread per item, twelve SHA-512 compressions each,
+ * the same instruction stream whatever the bytes are.  Device form: strides
+ * ck_stride, out_stride >= 64 (out1 and out2 share one), ikm_stride >=
+ * ikm_len. */
+int gvs_noise_hkdf(gvs_handle *h, const uint8_t *cks, const uint8_t *ikm, uint32_t ikm_len,
+                   uint32_t n, uint8_t *out1, uint8_t *out2);
+int gvs_noise_hkdf_device(gvs_handle *h, const void *d_cks, uint32_t ck_stride, const void *d_ikm,
+                          uint32_t ikm_stride, uint32_t ikm_len, uint32_t n,
+                          void *d_out1, void *d_out2, uint32_t out_stride);
+
 /* Message expiry (README.md:86-99: the untrusted host supplies the time and
  * the expiry period).  From the next batch on, messages whose timestamp is
  * < cutoff expire: each batch's message pass records up to X of them (fixed
