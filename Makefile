@@ -16,8 +16,9 @@ EDHOST := tests/libedhost.so
 CHACHAHOST := tests/libchachahost.so
 AEADHOST := tests/libaeadhost.so
 XHOST := tests/libxhost.so
+NHOST := tests/libnhost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST) $(NHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -49,11 +50,17 @@ $(AEADHOST): tests/aead_host.cpp grapevine_amd/csrc/gvs_aead.h grapevine_amd/csr
 $(XHOST): tests/x25519_host.cpp grapevine_amd/csrc/gvs_x25519.h grapevine_amd/csrc/gvs_ed25519.h grapevine_amd/csrc/gvs_sr25519.h grapevine_amd/csrc/gvs_device.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/x25519_host.cpp
 
+# the device Noise IX responder (the three phases of k_noise_ix over four lane
+# states, chained with the host ladder and the serial AES-256-GCM) built for
+# the CPU (tests/test_noise.py)
+$(NHOST): tests/noise_host.cpp tests/aead_host.cpp $(wildcard grapevine_amd/csrc/*.h)
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/noise_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST) $(NHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

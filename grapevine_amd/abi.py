@@ -101,6 +101,16 @@ AEAD_KEY_BYTES, AEAD_IV_BYTES, AEAD_TAG_BYTES, AEAD_AAD_MAX, AEAD_TEXT_MAX = 32,
 # the channel's key agreement (gvs_x25519: scalars, u-coordinates and results;
 # gvs_noise_hkdf: chaining keys and both outputs, ikm of 0 or X25519_BYTES)
 X25519_BYTES, NOISE_HKDF_BYTES = 32, 64
+# the Noise IX responder (gvs_noise_ix_respond): the limits of message 1's
+# payload and of the prologue, and message 2's bytes around its payload
+NOISE_PAYLOAD1_MAX, NOISE_PROLOGUE_MAX, NOISE_IX_MSG2_FIXED = 64, 64, 96
+_vp, _u32 = ctypes.c_void_p, ctypes.c_uint32
+# h, static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride,
+# msg1_lens, payload, payload_stride, payload_len, n, msg2, msg2_stride,
+# msg2_lens, recv_keys, send_keys, hashes, ok (gvs_noise_ix_respond and its
+# device form)
+NOISE_IX_RESPOND_ARGTYPES = [_vp, ctypes.c_char_p, ctypes.c_char_p, _u32, _vp, _vp, _u32, _vp, _vp, _u32,
+                             _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]
 
 
 def noise_iv(counter):

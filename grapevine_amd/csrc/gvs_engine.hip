@@ -34,6 +34,7 @@
 #include "gvs_sr25519.h"
 #include "gvs_ed25519.h"
 #include "gvs_x25519.h"
+#include "gvs_noise.h"
 #include "gvs_chacha.h"
 #include "gvs_aead.h"
 #include "gvs_spass.h"
@@ -3087,6 +3088,176 @@ int gvs_noise_hkdf(gvs_handle* h, const uint8_t* cks, const uint8_t* ikm, uint32
     return bounce_done(h, r);
   if (int r = d2h(h, out1, d + b, b)) return r;
   if (int r = d2h(h, out2, d + 2 * b, b)) return r;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return bounce_done(h, GVS_OK);
+}
+
+// ------------------------------------ the Noise IX responder (gvs_noise.h)
+
+static size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+struct NoiseIxCall {
+  const uint8_t* static_secret;  // host memory, 32 B
+  const uint8_t* prologue;       // host memory
+  uint32_t prologue_len;
+  const uint8_t* eph;            // device memory from here on
+  const uint8_t* msg1;
+  uint32_t msg1_stride;
+  const uint32_t* msg1_lens;
+  const uint8_t* payload;
+  uint32_t payload_stride, payload_len, n;
+  uint8_t* msg2;
+  uint32_t msg2_stride;
+  uint32_t* msg2_lens;
+  uint8_t *recv, *send, *hashes;
+  uint32_t* ok;
+};
+
+static bool noise_ix_call_ok(gvs_handle* h, const NoiseIxCall& c) {
+  return h && c.static_secret && c.prologue_len <= sr::kNxPrologueMax && (!c.prologue_len || c.prologue) &&
+         c.payload_len <= kAeadTextMax && (!c.payload_len || c.payload) &&
+         (!c.payload_stride || c.payload_stride >= c.payload_len) && c.msg1_stride >= 64 &&
+         (uint64_t)c.msg2_stride >= (uint64_t)sr::kNxMsg2Fixed + c.payload_len && c.n <= max_submit(h) &&
+         (!c.n || (c.eph && c.msg1 && c.msg1_lens && c.msg2 && c.msg2_lens && c.recv && c.send && c.ok));
+}
+
+// the second seal's text stride: payload 2 in whole 16-byte blocks
+static uint32_t noise_ix_text2(uint32_t p2) { return (uint32_t)up16(p2 ? p2 : 1); }
+
+// per-handshake state of the chain, in the device scratch
+static size_t noise_ix_work_bytes(uint32_t n, uint32_t p2) {
+  const size_t x = 4 * (size_t)n + 1, t2 = noise_ix_text2(p2);
+  return 3 * x * 32 + up16(x * 4) + 64 + (size_t)n * (128 + 32 + 64 + 32 + 48 + t2 + t2 + 16) +
+         up16((size_t)n * 12) + 4 * up16((size_t)n * 4);
+}
+
+// The chain on the handle's stream, synchronous: the gather, one k_x25519 over
+// 4n + 1 items, then k_noise_ix<A>, k_aead<true>, k_noise_ix<B>, k_aead<true>,
+// k_noise_ix<C>.  c's arrays are device memory; `work` holds
+// noise_ix_work_bytes, 16-byte aligned.
+static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
+  if (int r = aead_init(h)) return r;
+  const uint32_t n = c.n, p2 = c.payload_len, t2 = noise_ix_text2(p2);
+  const size_t x = 4 * (size_t)n + 1;
+  uint8_t* p = work;
+  auto take = [&](size_t bytes) {
+    uint8_t* q = p;
+    p += up16(bytes);
+    return q;
+  };
+  uint8_t *xsc = take(x * 32), *xpt = take(x * 32), *xout = take(x * 32);
+  uint32_t* xok = (uint32_t*)take(x * 4);
+  uint8_t *pro = take(64), *st = take((size_t)n * 128), *key = take((size_t)n * 32), *aad = take((size_t)n * 64),
+          *text1 = take((size_t)n * 32), *ct1 = take((size_t)n * 48), *text2 = take((size_t)n * t2),
+          *ct2 = take((size_t)n * (t2 + 16));
+  uint32_t* iv = (uint32_t*)take((size_t)n * 12);
+  uint32_t *aad_lens = (uint32_t*)take((size_t)n * 4), *len1 = (uint32_t*)take((size_t)n * 4),
+           *len2 = (uint32_t*)take((size_t)n * 4), *olens = (uint32_t*)take((size_t)n * 4);
+
+  sr::NxGatherArgs g{};
+  std::memcpy(g.s, c.static_secret, 32);
+  if (c.prologue_len) std::memcpy(g.pro, c.prologue, c.prologue_len);
+  g.eph = c.eph;
+  g.msg1 = c.msg1;
+  g.msg1_stride = c.msg1_stride;
+  g.payload = c.payload;
+  g.payload_stride = c.payload_stride;
+  g.p2 = p2;
+  g.text2_stride = t2;
+  g.n = n;
+  g.xsc = xsc, g.xpt = xpt, g.pro_out = pro, g.iv = iv;
+  g.aad_lens = aad_lens, g.len1 = len1, g.len2 = len2, g.text2 = text2;
+
+  sr::NxArgs a{};
+  a.n = n, a.p2 = p2, a.steps_c = sr::nx_steps_c(p2);
+  a.msg1 = c.msg1, a.msg1_stride = c.msg1_stride, a.msg1_lens = c.msg1_lens;
+  a.pro = pro, a.pro_len = c.prologue_len;
+  a.xout = xout, a.xok = xok;
+  a.st = st, a.key = key, a.aad = aad, a.text1 = text1, a.ct1 = ct1, a.ct2 = ct2, a.ct2_stride = t2 + 16;
+  a.msg2 = c.msg2, a.msg2_stride = c.msg2_stride, a.msg2_lens = c.msg2_lens;
+  a.recv = c.recv, a.send = c.send, a.hashes = c.hashes, a.ok = c.ok;
+
+  AeadArgs s1{};
+  s1.keys = (const uint4*)key, s1.ivs = iv, s1.aad = aad, s1.aad_stride = 64, s1.aad_lens = aad_lens;
+  s1.in = text1, s1.in_stride = 32, s1.in_lens = len1, s1.n = n;
+  s1.out = ct1, s1.out_stride = 48, s1.out_lens = olens;
+  AeadArgs s2 = s1;
+  s2.in = text2, s2.in_stride = t2, s2.in_lens = len2, s2.out = ct2, s2.out_stride = t2 + 16;
+
+  const dim3 grid((n + sr::kXItems - 1) / sr::kXItems), block(sr::kXThreads);
+  h->n_marks = 0;
+  mark(h, "start");
+  hipLaunchKernelGGL(sr::k_noise_ix_gather, grid, block, 0, h->stream, g);
+  enqueue_x25519(h, sr::XArgs{xsc, 32, xpt, 32, (uint32_t)x, xout, 32, xok});
+  mark(h, "x25519");
+  hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxA>, grid, block, 0, h->stream, a);
+  mark(h, "noise_a");
+  enqueue_aead(h, true, s1);
+  mark(h, "aead_seal");
+  hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxB>, grid, block, 0, h->stream, a);
+  mark(h, "noise_b");
+  enqueue_aead(h, true, s2);
+  mark(h, "aead_seal");
+  hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxC>, grid, block, 0, h->stream, a);
+  mark(h, "noise_c");
+  GVS_HIP(h, hipGetLastError());
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return GVS_OK;
+}
+
+int gvs_noise_ix_respond_device(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
+                                uint32_t prologue_len, const void* d_ephemerals, const void* d_msg1,
+                                uint32_t msg1_stride, const uint32_t* d_msg1_lens, const void* d_payload,
+                                uint32_t payload_stride, uint32_t payload_len, uint32_t n, void* d_msg2,
+                                uint32_t msg2_stride, uint32_t* d_msg2_lens, void* d_recv_keys,
+                                void* d_send_keys, void* d_hashes, uint32_t* d_ok) {
+  const NoiseIxCall c{static_secret, prologue, prologue_len, (const uint8_t*)d_ephemerals,
+                      (const uint8_t*)d_msg1, msg1_stride, d_msg1_lens, (const uint8_t*)d_payload,
+                      payload_stride, payload_len, n, (uint8_t*)d_msg2, msg2_stride, d_msg2_lens,
+                      (uint8_t*)d_recv_keys, (uint8_t*)d_send_keys, (uint8_t*)d_hashes, d_ok};
+  if (!noise_ix_call_ok(h, c)) return GVS_ERR_INVALID_ARG;
+  if (!n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  if (int r = dev_scratch(h, noise_ix_work_bytes(n, payload_len))) return r;
+  return noise_ix_run(h, c, h->sr_dev);
+}
+
+int gvs_noise_ix_respond(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
+                         uint32_t prologue_len, const uint8_t* ephemerals, const uint8_t* msg1,
+                         uint32_t msg1_stride, const uint32_t* msg1_lens, const uint8_t* payload,
+                         uint32_t payload_stride, uint32_t payload_len, uint32_t n, uint8_t* msg2,
+                         uint32_t msg2_stride, uint32_t* msg2_lens, uint8_t* recv_keys, uint8_t* send_keys,
+                         uint8_t* hashes, uint32_t* ok) {
+  NoiseIxCall c{static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride, msg1_lens, payload,
+                payload_stride, payload_len, n, msg2, msg2_stride, msg2_lens, recv_keys, send_keys, hashes, ok};
+  if (!noise_ix_call_ok(h, c)) return GVS_ERR_INVALID_ARG;
+  if (!n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  // the work area, then the caller's arrays: in (ephemerals, msg1, lens, payload), out
+  const size_t work = noise_ix_work_bytes(n, payload_len), b_e = (size_t)n * 32, b_m1 = up16((size_t)n * msg1_stride),
+               b_u32 = up16((size_t)n * 4), b_pay = up16(payload_stride ? (size_t)n * payload_stride : payload_len),
+               b_m2 = up16((size_t)n * msg2_stride), b_h = (size_t)n * 64;
+  if (int r = dev_scratch(h, work + b_e + b_m1 + b_u32 + b_pay + b_m2 + b_u32 + 2 * b_e + b_h + b_u32)) return r;
+  uint8_t* d = h->sr_dev + work;
+  uint8_t *d_e = d, *d_m1 = d_e + b_e, *d_l1 = d_m1 + b_m1, *d_pay = d_l1 + b_u32, *d_m2 = d_pay + b_pay,
+          *d_l2 = d_m2 + b_m2, *d_rk = d_l2 + b_u32, *d_sk = d_rk + b_e, *d_hh = d_sk + b_e, *d_ok = d_hh + b_h;
+  if (int r = bounce_begin(h)) return r;
+  if (int r = h2d(h, d_e, ephemerals, b_e)) return r;
+  if (int r = h2d(h, d_m1, msg1, (size_t)n * msg1_stride)) return r;
+  if (int r = h2d(h, d_l1, msg1_lens, (size_t)n * 4)) return r;
+  if (payload_len)
+    if (int r = h2d(h, d_pay, payload, payload_stride ? (size_t)n * payload_stride : payload_len)) return r;
+  c.eph = d_e, c.msg1 = d_m1, c.msg1_lens = (const uint32_t*)d_l1, c.payload = payload_len ? d_pay : nullptr;
+  c.msg2 = d_m2, c.msg2_lens = (uint32_t*)d_l2, c.recv = d_rk, c.send = d_sk;
+  c.hashes = hashes ? d_hh : nullptr, c.ok = (uint32_t*)d_ok;
+  if (int r = noise_ix_run(h, c, h->sr_dev)) return bounce_done(h, r);
+  if (int r = d2h(h, msg2, d_m2, (size_t)n * msg2_stride)) return r;
+  if (int r = d2h(h, msg2_lens, d_l2, (size_t)n * 4)) return r;
+  if (int r = d2h(h, recv_keys, d_rk, b_e)) return r;
+  if (int r = d2h(h, send_keys, d_sk, b_e)) return r;
+  if (hashes)
+    if (int r = d2h(h, hashes, d_hh, b_h)) return r;
+  if (int r = d2h(h, ok, d_ok, (size_t)n * 4)) return r;
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   return bounce_done(h, GVS_OK);
 }

@@ -40,6 +40,7 @@ EXPORTED = (
     "gvs_aead_open", "gvs_aead_open_device", "gvs_aead_seal", "gvs_aead_seal_device",
     "gvs_process_wire_batch_channel", "gvs_process_wire_batch_channel_device",
     "gvs_x25519", "gvs_x25519_device", "gvs_noise_hkdf", "gvs_noise_hkdf_device",
+    "gvs_noise_ix_respond", "gvs_noise_ix_respond_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -104,6 +105,8 @@ def load_library(path=None):
     lib.gvs_x25519_device.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp]
     lib.gvs_noise_hkdf.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     lib.gvs_noise_hkdf_device.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, u32]
+    lib.gvs_noise_ix_respond.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
+    lib.gvs_noise_ix_respond_device.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
     lib.gvs_wire_decode_device.argtypes =[vp, vp, u32, vp, u32, vp, vp, vp, vp]
     lib.gvs_wire_encode_device.argtypes = [vp, vp, u32, vp, u32, vp]
     lib.gvs_process_batches.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(u32)]
@@ -561,6 +564,52 @@ class ObliviousStore:
                                             32 if ikm is not None else 0, n, out1.ctypes.data,
                                             out2.ctypes.data))
         return out1, out2
+
+    def noise_ix_respond(self, static_secret, ephemerals, msg1, payload=b"", prologue=b"",
+                         msg2_stride=None):
+        """The responder's side of n Noise_IX_25519_AESGCM_SHA512 handshakes
+        on the device (gvs_noise_ix_respond): static_secret 32 bytes,
+        ephemerals (n, 32) fresh secrets, msg1 a list of n first messages,
+        payload one byte string for all or a list of n of one length, prologue
+        bytes -> (list of n second messages, recv_keys (n, 32), send_keys
+        (n, 32), hashes (n, 64), (n,) bool, the (n, stride) message-2 slab).  A
+        handshake that fails is b"" with zero keys and hash.  The form on
+        torch tensors is `noise_ix_respond_device`."""
+        n = len(msg1)
+        eph = np.ascontiguousarray(ephemerals, np.uint8).reshape(n, 32)
+        slab, lens, stride = self._wire_slab(msg1, max([len(m) for m in msg1] + [64]))
+        one = isinstance(payload, (bytes, bytearray))
+        pays = [bytes(payload)] if one else [bytes(p) for p in payload]
+        p2 = len(pays[0]) if pays else 0
+        if any(len(p) != p2 for p in pays) or (not one and len(pays) != n):
+            raise ValueError("noise_ix_respond: one payload length per call")
+        pay = np.frombuffer(b"".join(pays), np.uint8) if p2 else None
+        m2s = msg2_stride if msg2_stride is not None else 96 + p2
+        msg2 = np.zeros((n, max(m2s, 1)), np.uint8)
+        m2l, ok = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        rk, sk, hh = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros((n, 64), np.uint8)
+        self._check(self.lib.gvs_noise_ix_respond(
+            self.h, bytes(static_secret), bytes(prologue), len(prologue), eph.ctypes.data, slab.ctypes.data,
+            stride, lens.ctypes.data, pay.ctypes.data if pay is not None else None, 0 if one else p2, p2, n,
+            msg2.ctypes.data, m2s, m2l.ctypes.data, rk.ctypes.data, sk.ctypes.data, hh.ctypes.data,
+            ok.ctypes.data))
+        return [msg2[k, :m2l[k]].tobytes() for k in range(n)], rk, sk, hh, ok.astype(bool), msg2
+
+    def noise_ix_respond_device(self, static_secret, ephemerals, msg1, msg1_lens, payload, payload_len,
+                                msg2, msg2_lens, recv_keys, send_keys, hashes, ok, prologue=b""):
+        """gvs_noise_ix_respond_device on torch CUDA tensors: ephemerals
+        (n, >= 32 contiguous 32), msg1 (n, stride) uint8, msg1_lens (n,) int32,
+        payload (n, stride) uint8, a 1-D tensor (one payload for all) or None,
+        and the outputs msg2 (n, stride) uint8, msg2_lens (n,) int32,
+        recv_keys / send_keys (n, 32), hashes (n, 64) or None, ok (n,) int32,
+        all written in place.  The caller synchronises its own streams first."""
+        n = msg1.shape[0]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        pstride = 0 if payload is None or payload.dim() == 1 else payload.stride(0)
+        self._check(self.lib.gvs_noise_ix_respond_device(
+            self.h, bytes(static_secret), bytes(prologue), len(prologue), ptr(ephemerals), ptr(msg1),
+            msg1.stride(0), ptr(msg1_lens), ptr(payload), pstride, payload_len, n, ptr(msg2), msg2.stride(0),
+            ptr(msg2_lens), ptr(recv_keys), ptr(send_keys), ptr(hashes), ptr(ok)))
 
     def access(self, req):
         out = self.process_batch(np.asarray([req], dtype=abi.REQUEST_DTYPE) if not isinstance(req, np.ndarray) else req.reshape(1))

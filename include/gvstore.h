@@ -499,6 +499,50 @@ int gvs_noise_hkdf_device(gvs_handle *h, const void *d_cks, uint32_t ck_stride, 
                           uint32_t ikm_stride, uint32_t ikm_len, uint32_t n,
                           void *d_out1, void *d_out2, uint32_t out_stride);
 
+/* The responder's side of a Noise_IX_25519_AESGCM_SHA512 handshake (Noise
+ * specification rev. 34; -> e, s   <- e, ee, se, s, es), batched: from n first
+ * messages to n second messages and the two transport keys of each connection,
+ * in one call.  Handshake k reads msg1 + k*msg1_stride: the
+ * initiator's ephemeral and static public keys (32 B each, in clear) and a
+ * payload of msg1_lens[k] - 64 <= GVS_NOISE_PAYLOAD1_MAX bytes; it uses the
+ * ephemeral secret ephemerals[k] (32 B from the caller's CSPRNG, never reused),
+ * the responder's static secret and the prologue (at most
+ * GVS_NOISE_PROLOGUE_MAX bytes; both read from host memory by either form),
+ * and seals payload_len <= GVS_AEAD_TEXT_MAX bytes of payload into message 2:
+ * handshake k's at payload + k*payload_stride, or one payload for all with
+ * payload_stride = 0.  Out: msg2 + k*msg2_stride = e_pub 32 | sealed static
+ * key 48 | sealed payload payload_len + 16, msg2_lens[k] = 96 + payload_len,
+ * the rest of the slot zero (msg2_stride >= 96 + payload_len; every slot is
+ * written whole); recv_keys[k] and send_keys[k] (32 B each) are the
+ * initiator-to-responder and responder-to-initiator keys, the open_keys and
+ * seal_keys rows of gvs_process_wire_batch_channel, each direction's counter
+ * at 0; hashes[k] (64 B; hashes may be NULL) is the handshake hash.  ok[k] = 0,
+ * with a zero length, a zeroed slot and zero keys and hash, for a message 1
+ * shorter than 64 or longer than 64 + GVS_NOISE_PAYLOAD1_MAX bytes and for an
+ * all-zero DH result (a small-order key from the peer: gvs_x25519's ok); the
+ * call itself fails only for its own arguments (GVS_ERR_INVALID_ARG: a length
+ * or stride outside the limits above, msg1_stride < 64, a missing array).  n
+ * at most a batch; n = 0 is a no-op.  Synchronous on the handle's stream; the
+ * same instruction stream whatever keys and messages are.  The device form
+ * takes its arrays from device memory, any alignment. */
+#define GVS_NOISE_PAYLOAD1_MAX 64
+#define GVS_NOISE_PROLOGUE_MAX 64
+int gvs_noise_ix_respond(gvs_handle *h, const uint8_t static_secret[32],
+                         const uint8_t *prologue, uint32_t prologue_len,
+                         const uint8_t *ephemerals, const uint8_t *msg1, uint32_t msg1_stride,
+                         const uint32_t *msg1_lens, const uint8_t *payload,
+                         uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                         uint8_t *msg2, uint32_t msg2_stride, uint32_t *msg2_lens,
+                         uint8_t *recv_keys, uint8_t *send_keys, uint8_t *hashes, uint32_t *ok);
+int gvs_noise_ix_respond_device(gvs_handle *h, const uint8_t static_secret[32],
+                                const uint8_t *prologue, uint32_t prologue_len,
+                                const void *d_ephemerals, const void *d_msg1, uint32_t msg1_stride,
+                                const uint32_t *d_msg1_lens, const void *d_payload,
+                                uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                                void *d_msg2, uint32_t msg2_stride, uint32_t *d_msg2_lens,
+                                void *d_recv_keys, void *d_send_keys, void *d_hashes,
+                                uint32_t *d_ok);
+
 /* Message expiry (README.md:86-99: the untrusted host supplies the time and
  * the expiry period).  From the next batch on, messages whose timestamp is
  * < cutoff expire: each batch's message pass records up to X of them (fixed
