@@ -15,10 +15,11 @@ SRHOST := tests/libsrhost.so
 EDHOST := tests/libedhost.so
 CHACHAHOST := tests/libchachahost.so
 AEADHOST := tests/libaeadhost.so
+AEADLONGHOST := tests/libaeadlonghost.so
 XHOST := tests/libxhost.so
 NHOST := tests/libnhost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST) $(NHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -45,6 +46,11 @@ $(CHACHAHOST): tests/chacha_host.cpp grapevine_amd/csrc/gvs_chacha.h
 $(AEADHOST): tests/aead_host.cpp grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/aead_host.cpp
 
+# the long channel cipher's schedule (256 thread states stepped through the
+# phases of k_aead_long) built for the CPU (tests/test_aead_long.py)
+$(AEADLONGHOST): tests/aead_long_host.cpp tests/aead_host.cpp grapevine_amd/csrc/gvs_aead_long.h grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/aead_long_host.cpp
+
 # the device X25519 quad ladder (four lane states stepped in a loop) and the
 # Noise HKDF built for the CPU (tests/test_x25519.py)
 $(XHOST): tests/x25519_host.cpp grapevine_amd/csrc/gvs_x25519.h grapevine_amd/csrc/gvs_ed25519.h grapevine_amd/csrc/gvs_sr25519.h grapevine_amd/csrc/gvs_device.h
@@ -60,7 +66,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(XHOST) $(NHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -97,6 +97,9 @@ WIRE_OK, WIRE_DECODE_ERROR, WIRE_BAD_FIELD, WIRE_BAD_SIGNATURE = 0, 1, 2, 3
 WIRE_BAD_CHANNEL_TAG = 4  # GVS_WIRE_BAD_CHANNEL_TAG: the request's channel tag does not verify
 # the channel cipher (gvs_aead_open / gvs_aead_seal: AES-256-GCM)
 AEAD_KEY_BYTES, AEAD_IV_BYTES, AEAD_TAG_BYTES, AEAD_AAD_MAX, AEAD_TEXT_MAX = 32, 12, 16, 64, WIRE_SLOT_MAX
+# the long form (gvs_aead_open_long / gvs_aead_seal_long): a whole Noise
+# message, and the cap on what one host-form call stages through the device
+AEAD_LONG_TEXT_MAX, AEAD_LONG_STAGE_MAX = 65519, 256 << 20
 
 # the channel's key agreement (gvs_x25519: scalars, u-coordinates and results;
 # gvs_noise_hkdf: chaining keys and both outputs, ikm of 0 or X25519_BYTES)

@@ -37,6 +37,7 @@
 #include "gvs_noise.h"
 #include "gvs_chacha.h"
 #include "gvs_aead.h"
+#include "gvs_aead_long.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
 #ifndef GVS_MA_EXTRA_LDS
@@ -2551,6 +2552,16 @@ static void enqueue_aead(gvs_handle* h, bool seal, AeadArgs a) {
     hipLaunchKernelGGL(k_aead<false>, grid, block, 0, h->stream, a);
 }
 
+// the long form (gvs_aead_long.h): one workgroup per message
+static void enqueue_aead_long(gvs_handle* h, bool seal, AeadArgs a) {
+  if (!a.n) return;
+  a.te = h->te;
+  if (seal)
+    hipLaunchKernelGGL(k_aead_long<true>, dim3(a.n), dim3(kAlThreads), 0, h->stream, a);
+  else
+    hipLaunchKernelGGL(k_aead_long<false>, dim3(a.n), dim3(kAlThreads), 0, h->stream, a);
+}
+
 // decode -> (challenge check) -> the batch -> encode, all on the engine
 // stream; the request and response slabs live in the handle's host-API
 // staging.
@@ -3280,16 +3291,19 @@ struct AeadCall {
   uint32_t* ok;
 };
 
-static bool aead_stride_ok(uint32_t s) { return s >= 16 && s % 16 == 0 && s <= kAeadTextMax + kAeadTag; }
+// lng: the long calls (k_aead_long), with their limits
+static bool aead_stride_ok(uint32_t s, bool lng) {
+  return s >= 16 && s % 16 == 0 && s <= (lng ? kAeadLongStrideMax : kAeadTextMax + kAeadTag);
+}
 
-static bool aead_call_ok(gvs_handle* h, const AeadCall& c, bool seal) {
-  return h && c.n <= max_submit(h) && aead_stride_ok(c.in_stride) && aead_stride_ok(c.out_stride) &&
+static bool aead_call_ok(gvs_handle* h, const AeadCall& c, bool seal, bool lng) {
+  return h && c.n <= max_submit(h) && aead_stride_ok(c.in_stride, lng) && aead_stride_ok(c.out_stride, lng) &&
          (!c.aad || (c.aad_lens && c.aad_stride >= 16 && c.aad_stride % 16 == 0)) &&
          (!c.n || (c.keys && c.ivs && c.in && c.in_lens && c.out && c.out_lens && (seal || c.ok)));
 }
 
-static int aead_device(gvs_handle* h, const AeadCall& c, bool seal) {
-  if (!aead_call_ok(h, c, seal) || !aligned16(c.keys) || !aligned16(c.aad) || !aligned16(c.in) ||
+static int aead_device(gvs_handle* h, const AeadCall& c, bool seal, bool lng) {
+  if (!aead_call_ok(h, c, seal, lng) || !aligned16(c.keys) || !aligned16(c.aad) || !aligned16(c.in) ||
       !aligned16(c.out) || ((uintptr_t)c.ivs & 3u))
     return GVS_ERR_INVALID_ARG;
   GVS_HIP(h, hipSetDevice(h->device));
@@ -3308,16 +3322,18 @@ static int aead_device(gvs_handle* h, const AeadCall& c, bool seal) {
   a.out_stride = c.out_stride;
   a.out_lens = c.out_lens;
   a.ok = c.ok;
+  if (lng) return launch_sync(h, seal ? "aead_seal_long" : "aead_open_long", [&] { enqueue_aead_long(h, seal, a); });
   return launch_sync(h, seal ? "aead_seal" : "aead_open", [&] { enqueue_aead(h, seal, a); });
 }
 
 // the host forms: the lengths are checked here (the device forms fail such a
 // message alone), then everything goes through the device scratch
-static int aead_host(gvs_handle* h, const AeadCall& c, bool seal) {
-  if (!aead_call_ok(h, c, seal)) return GVS_ERR_INVALID_ARG;
+static int aead_host(gvs_handle* h, const AeadCall& c, bool seal, bool lng) {
+  if (!aead_call_ok(h, c, seal, lng)) return GVS_ERR_INVALID_ARG;
+  const uint32_t text_max = lng ? kAeadLongTextMax : kAeadTextMax;
   for (uint32_t k = 0; k < c.n; ++k) {
     const uint32_t len = c.in_lens[k], text = seal ? len : (len < kAeadTag ? 0u : len - kAeadTag);
-    if (len > c.in_stride || text > kAeadTextMax || text + (seal ? kAeadTag : 0u) > c.out_stride ||
+    if (len > c.in_stride || text > text_max || text + (seal ? kAeadTag : 0u) > c.out_stride ||
         (c.aad && (c.aad_lens[k] > kAeadAadMax || c.aad_lens[k] > c.aad_stride)))
       return GVS_ERR_INVALID_ARG;
   }
@@ -3326,7 +3342,9 @@ static int aead_host(gvs_handle* h, const AeadCall& c, bool seal) {
   const size_t n = c.n, b_key = n * 32, b_iv = (n * kAeadIv + 15) & ~(size_t)15,
                b_aad = c.aad ? n * c.aad_stride : 0, b_in = n * c.in_stride, b_out = n * c.out_stride,
                b_u32 = (n * 4 + 15) & ~(size_t)15;
-  if (int r = dev_scratch(h, b_key + b_iv + b_aad + b_in + b_out + 4 * b_u32)) return r;
+  const size_t b_all = b_key + b_iv + b_aad + b_in + b_out + 4 * b_u32;
+  if (lng && b_all > (size_t)GVS_AEAD_LONG_STAGE_MAX) return GVS_ERR_INVALID_ARG;  // before any allocation
+  if (int r = dev_scratch(h, b_all)) return r;
   uint8_t* d = h->sr_dev;  // every part 16-byte aligned
   uint8_t *d_iv = d + b_key, *d_aad = d_iv + b_iv, *d_in = d_aad + b_aad, *d_out = d_in + b_in;
   uint32_t* d_u32[4];  // aad_lens, in_lens, out_lens, ok
@@ -3342,7 +3360,7 @@ static int aead_host(gvs_handle* h, const AeadCall& c, bool seal) {
   if (int r = h2d(h, d_u32[1], c.in_lens, n * 4)) return r;
   const AeadCall dc{d, d_iv, c.aad ? d_aad : nullptr, c.aad_stride, d_u32[0], d_in, c.in_stride, d_u32[1],
                     c.n, d_out, c.out_stride, d_u32[2], d_u32[3]};
-  if (int r = aead_device(h, dc, seal)) return bounce_done(h, r);
+  if (int r = aead_device(h, dc, seal, lng)) return bounce_done(h, r);
   if (int r = d2h(h, c.out, d_out, b_out)) return r;
   if (int r = d2h(h, c.out_lens, d_u32[2], n * 4)) return r;
   if (c.ok)
@@ -3356,7 +3374,7 @@ int gvs_aead_open_device(gvs_handle* h, const void* d_keys, const void* d_ivs, c
                          uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
                          uint32_t out_stride, uint32_t* d_out_lens, uint32_t* d_ok) {
   return aead_device(h, AeadCall{d_keys, d_ivs, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
-                                 d_out, out_stride, d_out_lens, d_ok}, false);
+                                 d_out, out_stride, d_out_lens, d_ok}, false, false);
 }
 
 int gvs_aead_seal_device(gvs_handle* h, const void* d_keys, const void* d_ivs, const void* d_aad,
@@ -3364,7 +3382,7 @@ int gvs_aead_seal_device(gvs_handle* h, const void* d_keys, const void* d_ivs, c
                          uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
                          uint32_t out_stride, uint32_t* d_out_lens) {
   return aead_device(h, AeadCall{d_keys, d_ivs, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
-                                 d_out, out_stride, d_out_lens, nullptr}, true);
+                                 d_out, out_stride, d_out_lens, nullptr}, true, false);
 }
 
 int gvs_aead_open(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const uint8_t* aad,
@@ -3372,7 +3390,7 @@ int gvs_aead_open(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const 
                   const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
                   uint32_t* out_lens, uint32_t* ok) {
   return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
-                               out_stride, out_lens, ok}, false);
+                               out_stride, out_lens, ok}, false, false);
 }
 
 int gvs_aead_seal(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const uint8_t* aad,
@@ -3380,7 +3398,40 @@ int gvs_aead_seal(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const 
                   const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
                   uint32_t* out_lens) {
   return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
-                               out_stride, out_lens, nullptr}, true);
+                               out_stride, out_lens, nullptr}, true, false);
+}
+
+// the long forms: the same argument lists, k_aead_long and its limits
+int gvs_aead_open_long_device(gvs_handle* h, const void* d_keys, const void* d_ivs, const void* d_aad,
+                              uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                              uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                              uint32_t out_stride, uint32_t* d_out_lens, uint32_t* d_ok) {
+  return aead_device(h, AeadCall{d_keys, d_ivs, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, d_ok}, false, true);
+}
+
+int gvs_aead_seal_long_device(gvs_handle* h, const void* d_keys, const void* d_ivs, const void* d_aad,
+                              uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                              uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                              uint32_t out_stride, uint32_t* d_out_lens) {
+  return aead_device(h, AeadCall{d_keys, d_ivs, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, nullptr}, true, true);
+}
+
+int gvs_aead_open_long(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const uint8_t* aad,
+                       uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                       const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                       uint32_t* out_lens, uint32_t* ok) {
+  return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, ok}, false, true);
+}
+
+int gvs_aead_seal_long(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const uint8_t* aad,
+                       uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                       const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                       uint32_t* out_lens) {
+  return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, nullptr}, true, true);
 }
 
 int gvs_set_expiry_cutoff(gvs_handle* h, uint64_t cutoff) {

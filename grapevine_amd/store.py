@@ -38,6 +38,7 @@ EXPORTED = (
     "gvs_challenge_derive", "gvs_challenge_derive_device", "gvs_process_wire_batch_seeded",
     "gvs_process_wire_batch_seeded_device", "gvs_process_wire_batches_seeded",
     "gvs_aead_open", "gvs_aead_open_device", "gvs_aead_seal", "gvs_aead_seal_device",
+    "gvs_aead_open_long", "gvs_aead_open_long_device", "gvs_aead_seal_long", "gvs_aead_seal_long_device",
     "gvs_process_wire_batch_channel", "gvs_process_wire_batch_channel_device",
     "gvs_x25519", "gvs_x25519_device", "gvs_noise_hkdf", "gvs_noise_hkdf_device",
     "gvs_noise_ix_respond", "gvs_noise_ix_respond_device",
@@ -93,6 +94,8 @@ def load_library(path=None):
     lib.gvs_aead_open_device.argtypes = lib.gvs_aead_open.argtypes
     lib.gvs_aead_seal.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp]
     lib.gvs_aead_seal_device.argtypes = lib.gvs_aead_seal.argtypes
+    lib.gvs_aead_open_long.argtypes = lib.gvs_aead_open_long_device.argtypes = lib.gvs_aead_open.argtypes
+    lib.gvs_aead_seal_long.argtypes = lib.gvs_aead_seal_long_device.argtypes = lib.gvs_aead_seal.argtypes
     lib.gvs_challenge_derive.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_challenge_derive_device.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_sr25519_verify.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp]
@@ -447,7 +450,7 @@ class ObliviousStore:
             chal.ctypes.data))
         return [out[k, :out_lens[k]].tobytes() for k in range(n)], sigs, status, chal
 
-    def _aead(self, seal, keys, ivs, msgs, aads):
+    def _aead(self, seal, keys, ivs, msgs, aads, long=False):
         n = len(msgs)
         keys = np.ascontiguousarray(keys, np.uint8).reshape(n, 32)
         ivs = np.ascontiguousarray(ivs, np.uint8).reshape(n, 12)
@@ -461,7 +464,7 @@ class ObliviousStore:
         out = np.zeros((n, out_stride), np.uint8)
         out_lens = np.zeros(n, np.uint32)
         ok = np.ones(n, np.uint32)
-        fn = self.lib.gvs_aead_seal if seal else self.lib.gvs_aead_open
+        fn = getattr(self.lib, ("gvs_aead_seal" if seal else "gvs_aead_open") + ("_long" if long else ""))
         self._check(fn(self.h, keys.ctypes.data, ivs.ctypes.data,
                        aad.ctypes.data if aad is not None else None, aad_stride,
                        aad_lens.ctypes.data if aad is not None else None, slab.ctypes.data, stride,
@@ -482,6 +485,18 @@ class ObliviousStore:
         the (n, stride) output slab); a message that does not verify is b""
         and its slot all zero."""
         out, out_lens, ok = self._aead(False, keys, ivs, msgs, aads)
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))], ok, out
+
+    def aead_seal_long(self, keys, ivs, msgs, aads=None):
+        """aead_seal for whole Noise messages (gvs_aead_seal_long): plaintexts
+        of up to abi.AEAD_LONG_TEXT_MAX bytes, one workgroup per message."""
+        out, out_lens, _ = self._aead(True, keys, ivs, msgs, aads, long=True)
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))]
+
+    def aead_open_long(self, keys, ivs, msgs, aads=None):
+        """aead_open for whole Noise messages (gvs_aead_open_long): ciphertext
+        | tag of up to 65 535 bytes -> (plaintexts, verdicts, output slab)."""
+        out, out_lens, ok = self._aead(False, keys, ivs, msgs, aads, long=True)
         return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))], ok, out
 
     def challenge_derive(self, seeds, draws):

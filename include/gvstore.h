@@ -415,6 +415,35 @@ int gvs_aead_seal_device(gvs_handle *h, const void *d_keys, const void *d_ivs, c
                          uint32_t in_stride, const uint32_t *d_in_lens, uint32_t n, void *d_out,
                          uint32_t out_stride, uint32_t *d_out_lens);
 
+/* The long form of the same cipher, for whole Noise messages (ciphertext + tag
+ * <= 65 535 bytes): the argument lists, the outputs and the per-message
+ * failures of gvs_aead_open / gvs_aead_seal, with a text of at most
+ * GVS_AEAD_LONG_TEXT_MAX bytes and strides (multiples of 16) of at most
+ * 65 536.  One 256-thread workgroup per message; texts of 0 .. GVS_AEAD_TEXT_MAX
+ * bytes are valid and give the bytes of the short calls, which stay the
+ * faster ones for them.  The host forms stage keys, IVs, AAD, input, output
+ * and lengths through device memory: a call whose arrays together pass
+ * GVS_AEAD_LONG_STAGE_MAX bytes is GVS_ERR_INVALID_ARG before anything is
+ * allocated (split it, or use the device forms, which stage nothing). */
+#define GVS_AEAD_LONG_TEXT_MAX 65519
+#define GVS_AEAD_LONG_STAGE_MAX (256u << 20)
+int gvs_aead_open_long(gvs_handle *h, const uint8_t *keys, const uint8_t *ivs, const uint8_t *aad,
+                       uint32_t aad_stride, const uint32_t *aad_lens, const uint8_t *in,
+                       uint32_t in_stride, const uint32_t *in_lens, uint32_t n, uint8_t *out,
+                       uint32_t out_stride, uint32_t *out_lens, uint32_t *ok);
+int gvs_aead_open_long_device(gvs_handle *h, const void *d_keys, const void *d_ivs, const void *d_aad,
+                              uint32_t aad_stride, const uint32_t *d_aad_lens, const void *d_in,
+                              uint32_t in_stride, const uint32_t *d_in_lens, uint32_t n, void *d_out,
+                              uint32_t out_stride, uint32_t *d_out_lens, uint32_t *d_ok);
+int gvs_aead_seal_long(gvs_handle *h, const uint8_t *keys, const uint8_t *ivs, const uint8_t *aad,
+                       uint32_t aad_stride, const uint32_t *aad_lens, const uint8_t *in,
+                       uint32_t in_stride, const uint32_t *in_lens, uint32_t n, uint8_t *out,
+                       uint32_t out_stride, uint32_t *out_lens);
+int gvs_aead_seal_long_device(gvs_handle *h, const void *d_keys, const void *d_ivs, const void *d_aad,
+                              uint32_t aad_stride, const uint32_t *d_aad_lens, const void *d_in,
+                              uint32_t in_stride, const uint32_t *d_in_lens, uint32_t n, void *d_out,
+                              uint32_t out_stride, uint32_t *d_out_lens);
+
 /* The challenge stream alone: out[k] (32 B) = draw number draws[k] of
  * ChaCha20Rng(seeds[k]), that is bytes [32*(d&1), 32*(d&1)+32) of ChaCha20
  * block d >> 1 under key seeds[k] (rand_chacha's layout: 64-bit block counter,
