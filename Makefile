@@ -18,8 +18,9 @@ AEADHOST := tests/libaeadhost.so
 AEADLONGHOST := tests/libaeadlonghost.so
 XHOST := tests/libxhost.so
 NHOST := tests/libnhost.so
+NLONGHOST := tests/libnlonghost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -62,11 +63,16 @@ $(XHOST): tests/x25519_host.cpp grapevine_amd/csrc/gvs_x25519.h grapevine_amd/cs
 $(NHOST): tests/noise_host.cpp tests/aead_host.cpp $(wildcard grapevine_amd/csrc/*.h)
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/noise_host.cpp
 
+# the long responder (phases A and B as above, then k_noise_ix_tail's schedule
+# in a loop over the handshakes) built for the CPU (tests/test_noise_long.py)
+$(NLONGHOST): tests/noise_long_host.cpp tests/noise_host.cpp tests/aead_host.cpp $(wildcard grapevine_amd/csrc/*.h)
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/noise_long_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -107,6 +107,8 @@ X25519_BYTES, NOISE_HKDF_BYTES = 32, 64
 # the Noise IX responder (gvs_noise_ix_respond): the limits of message 1's
 # payload and of the prologue, and message 2's bytes around its payload
 NOISE_PAYLOAD1_MAX, NOISE_PROLOGUE_MAX, NOISE_IX_MSG2_FIXED = 64, 64, 96
+# gvs_noise_ix_respond_long: message 2 = 96 + payload <= 65 535, Noise's limit
+NOISE_PAYLOAD2_LONG_MAX = 65439
 _vp, _u32 = ctypes.c_void_p, ctypes.c_uint32
 # h, static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride,
 # msg1_lens, payload, payload_stride, payload_len, n, msg2, msg2_stride,

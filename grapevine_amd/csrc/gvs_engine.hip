@@ -38,6 +38,7 @@
 #include "gvs_chacha.h"
 #include "gvs_aead.h"
 #include "gvs_aead_long.h"
+#include "gvs_noise_long.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
 #ifndef GVS_MA_EXTRA_LDS
@@ -3122,33 +3123,47 @@ struct NoiseIxCall {
   uint32_t* msg2_lens;
   uint8_t *recv, *send, *hashes;
   uint32_t* ok;
+  bool lng = false;  // the long calls: k_aead_long and k_noise_ix_tail (gvs_noise_long.h), with their limits
 };
 
 static bool noise_ix_call_ok(gvs_handle* h, const NoiseIxCall& c) {
   return h && c.static_secret && c.prologue_len <= sr::kNxPrologueMax && (!c.prologue_len || c.prologue) &&
-         c.payload_len <= kAeadTextMax && (!c.payload_len || c.payload) &&
+         c.payload_len <= (c.lng ? sr::kNxPayload2LongMax : kAeadTextMax) && (!c.payload_len || c.payload) &&
          (!c.payload_stride || c.payload_stride >= c.payload_len) && c.msg1_stride >= 64 &&
          (uint64_t)c.msg2_stride >= (uint64_t)sr::kNxMsg2Fixed + c.payload_len && c.n <= max_submit(h) &&
+         (!c.lng || (c.msg2_stride % 16 == 0 && c.msg2_stride <= kAeadLongStrideMax && c.payload_stride % 16 == 0)) &&
          (!c.n || (c.eph && c.msg1 && c.msg1_lens && c.msg2 && c.msg2_lens && c.recv && c.send && c.ok));
 }
 
-// the second seal's text stride: payload 2 in whole 16-byte blocks
-static uint32_t noise_ix_text2(uint32_t p2) { return (uint32_t)up16(p2 ? p2 : 1); }
+// The second seal's text stride: payload 2 in whole 16-byte blocks.  The long
+// chain hands k_aead_long the caller's own rows (0: no text rows in the work
+// area); only one payload for all is spread into rows, because the kernel
+// refuses a message longer than its in_stride and so cannot read it in place.
+static uint32_t noise_ix_text2(const NoiseIxCall& c) {
+  if (c.lng) return c.payload_len && !c.payload_stride ? (uint32_t)up16(c.payload_len) : 0u;
+  return (uint32_t)up16(c.payload_len ? c.payload_len : 1);
+}
+
+// and its output stride: ct_p's rows
+static uint32_t noise_ix_ct2(const NoiseIxCall& c) {
+  return c.lng ? sr::nt_row(c.payload_len) : noise_ix_text2(c) + 16;
+}
 
 // per-handshake state of the chain, in the device scratch
-static size_t noise_ix_work_bytes(uint32_t n, uint32_t p2) {
-  const size_t x = 4 * (size_t)n + 1, t2 = noise_ix_text2(p2);
-  return 3 * x * 32 + up16(x * 4) + 64 + (size_t)n * (128 + 32 + 64 + 32 + 48 + t2 + t2 + 16) +
-         up16((size_t)n * 12) + 4 * up16((size_t)n * 4);
+static size_t noise_ix_work_bytes(const NoiseIxCall& c) {
+  const size_t n = c.n, x = 4 * n + 1;
+  return 3 * x * 32 + up16(x * 4) + 64 + n * (128 + 32 + 64 + 32 + 48 + noise_ix_text2(c) + noise_ix_ct2(c)) +
+         up16(n * 12) + 4 * up16(n * 4);
 }
 
 // The chain on the handle's stream, synchronous: the gather, one k_x25519 over
 // 4n + 1 items, then k_noise_ix<A>, k_aead<true>, k_noise_ix<B>, k_aead<true>,
-// k_noise_ix<C>.  c's arrays are device memory; `work` holds
+// k_noise_ix<C>; the long chain ends with k_aead_long<true> and
+// k_noise_ix_tail instead.  c's arrays are device memory; `work` holds
 // noise_ix_work_bytes, 16-byte aligned.
 static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   if (int r = aead_init(h)) return r;
-  const uint32_t n = c.n, p2 = c.payload_len, t2 = noise_ix_text2(p2);
+  const uint32_t n = c.n, p2 = c.payload_len, t2 = noise_ix_text2(c), c2 = noise_ix_ct2(c);
   const size_t x = 4 * (size_t)n + 1;
   uint8_t* p = work;
   auto take = [&](size_t bytes) {
@@ -3160,7 +3175,7 @@ static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   uint32_t* xok = (uint32_t*)take(x * 4);
   uint8_t *pro = take(64), *st = take((size_t)n * 128), *key = take((size_t)n * 32), *aad = take((size_t)n * 64),
           *text1 = take((size_t)n * 32), *ct1 = take((size_t)n * 48), *text2 = take((size_t)n * t2),
-          *ct2 = take((size_t)n * (t2 + 16));
+          *ct2 = take((size_t)n * c2);
   uint32_t* iv = (uint32_t*)take((size_t)n * 12);
   uint32_t *aad_lens = (uint32_t*)take((size_t)n * 4), *len1 = (uint32_t*)take((size_t)n * 4),
            *len2 = (uint32_t*)take((size_t)n * 4), *olens = (uint32_t*)take((size_t)n * 4);
@@ -3174,17 +3189,17 @@ static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   g.payload = c.payload;
   g.payload_stride = c.payload_stride;
   g.p2 = p2;
-  g.text2_stride = t2;
+  g.text2_stride = c.lng ? 0 : t2;  // the long chain's text is not copied byte by byte
   g.n = n;
   g.xsc = xsc, g.xpt = xpt, g.pro_out = pro, g.iv = iv;
   g.aad_lens = aad_lens, g.len1 = len1, g.len2 = len2, g.text2 = text2;
 
   sr::NxArgs a{};
-  a.n = n, a.p2 = p2, a.steps_c = sr::nx_steps_c(p2);
+  a.n = n, a.p2 = p2, a.steps_c = c.lng ? sr::nt_steps(p2) : sr::nx_steps_c(p2);
   a.msg1 = c.msg1, a.msg1_stride = c.msg1_stride, a.msg1_lens = c.msg1_lens;
   a.pro = pro, a.pro_len = c.prologue_len;
   a.xout = xout, a.xok = xok;
-  a.st = st, a.key = key, a.aad = aad, a.text1 = text1, a.ct1 = ct1, a.ct2 = ct2, a.ct2_stride = t2 + 16;
+  a.st = st, a.key = key, a.aad = aad, a.text1 = text1, a.ct1 = ct1, a.ct2 = ct2, a.ct2_stride = c2;
   a.msg2 = c.msg2, a.msg2_stride = c.msg2_stride, a.msg2_lens = c.msg2_lens;
   a.recv = c.recv, a.send = c.send, a.hashes = c.hashes, a.ok = c.ok;
 
@@ -3193,12 +3208,21 @@ static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   s1.in = text1, s1.in_stride = 32, s1.in_lens = len1, s1.n = n;
   s1.out = ct1, s1.out_stride = 48, s1.out_lens = olens;
   AeadArgs s2 = s1;
-  s2.in = text2, s2.in_stride = t2, s2.in_lens = len2, s2.out = ct2, s2.out_stride = t2 + 16;
+  s2.in = text2, s2.in_stride = t2, s2.in_lens = len2, s2.out = ct2, s2.out_stride = c2;
+  if (c.lng && !t2) {  // the caller's rows as they stand; an empty payload reads nothing
+    s2.in = p2 ? c.payload : ct2;
+    s2.in_stride = p2 ? c.payload_stride : 16;
+  }
 
   const dim3 grid((n + sr::kXItems - 1) / sr::kXItems), block(sr::kXThreads);
   h->n_marks = 0;
   mark(h, "start");
   hipLaunchKernelGGL(sr::k_noise_ix_gather, grid, block, 0, h->stream, g);
+  if (c.lng && t2) {
+    const sr::NxSpreadArgs sp{c.payload, p2, t2, n, text2};
+    hipLaunchKernelGGL(sr::k_noise_ix_spread, dim3((uint32_t)(((uint64_t)n * (t2 / 16) + 255) / 256)), dim3(256), 0,
+                       h->stream, sp);
+  }
   enqueue_x25519(h, sr::XArgs{xsc, 32, xpt, 32, (uint32_t)x, xout, 32, xok});
   mark(h, "x25519");
   hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxA>, grid, block, 0, h->stream, a);
@@ -3207,48 +3231,53 @@ static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   mark(h, "aead_seal");
   hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxB>, grid, block, 0, h->stream, a);
   mark(h, "noise_b");
-  enqueue_aead(h, true, s2);
-  mark(h, "aead_seal");
-  hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxC>, grid, block, 0, h->stream, a);
-  mark(h, "noise_c");
+  if (c.lng) {
+    enqueue_aead_long(h, true, s2);
+    mark(h, "aead_seal_long");
+    hipLaunchKernelGGL(sr::k_noise_ix_tail, dim3((n + sr::kSrThreads - 1) / sr::kSrThreads), dim3(sr::kSrThreads), 0,
+                       h->stream, a);
+    mark(h, "noise_tail");
+  } else {
+    enqueue_aead(h, true, s2);
+    mark(h, "aead_seal");
+    hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxC>, grid, block, 0, h->stream, a);
+    mark(h, "noise_c");
+  }
   GVS_HIP(h, hipGetLastError());
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   return GVS_OK;
 }
 
-int gvs_noise_ix_respond_device(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
-                                uint32_t prologue_len, const void* d_ephemerals, const void* d_msg1,
-                                uint32_t msg1_stride, const uint32_t* d_msg1_lens, const void* d_payload,
-                                uint32_t payload_stride, uint32_t payload_len, uint32_t n, void* d_msg2,
-                                uint32_t msg2_stride, uint32_t* d_msg2_lens, void* d_recv_keys,
-                                void* d_send_keys, void* d_hashes, uint32_t* d_ok) {
-  const NoiseIxCall c{static_secret, prologue, prologue_len, (const uint8_t*)d_ephemerals,
-                      (const uint8_t*)d_msg1, msg1_stride, d_msg1_lens, (const uint8_t*)d_payload,
-                      payload_stride, payload_len, n, (uint8_t*)d_msg2, msg2_stride, d_msg2_lens,
-                      (uint8_t*)d_recv_keys, (uint8_t*)d_send_keys, (uint8_t*)d_hashes, d_ok};
+// the device forms; the long one's work area has a cap (before any allocation)
+// and its 16-byte words want aligned rows
+static int noise_ix_device(gvs_handle* h, const NoiseIxCall& c) {
   if (!noise_ix_call_ok(h, c)) return GVS_ERR_INVALID_ARG;
-  if (!n) return GVS_OK;
+  if (c.lng && (!aligned16(c.msg2) || !aligned16(c.payload) || noise_ix_work_bytes(c) > (size_t)GVS_AEAD_LONG_STAGE_MAX))
+    return GVS_ERR_INVALID_ARG;
+  if (!c.n) return GVS_OK;
   GVS_HIP(h, hipSetDevice(h->device));
-  if (int r = dev_scratch(h, noise_ix_work_bytes(n, payload_len))) return r;
+  if (int r = dev_scratch(h, noise_ix_work_bytes(c))) return r;
   return noise_ix_run(h, c, h->sr_dev);
 }
 
-int gvs_noise_ix_respond(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
-                         uint32_t prologue_len, const uint8_t* ephemerals, const uint8_t* msg1,
-                         uint32_t msg1_stride, const uint32_t* msg1_lens, const uint8_t* payload,
-                         uint32_t payload_stride, uint32_t payload_len, uint32_t n, uint8_t* msg2,
-                         uint32_t msg2_stride, uint32_t* msg2_lens, uint8_t* recv_keys, uint8_t* send_keys,
-                         uint8_t* hashes, uint32_t* ok) {
-  NoiseIxCall c{static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride, msg1_lens, payload,
-                payload_stride, payload_len, n, msg2, msg2_stride, msg2_lens, recv_keys, send_keys, hashes, ok};
+// the host forms: everything goes through the device scratch, in 16-byte-aligned parts
+static int noise_ix_host(gvs_handle* h, NoiseIxCall c) {
   if (!noise_ix_call_ok(h, c)) return GVS_ERR_INVALID_ARG;
-  if (!n) return GVS_OK;
-  GVS_HIP(h, hipSetDevice(h->device));
+  const uint32_t n = c.n, msg1_stride = c.msg1_stride, payload_stride = c.payload_stride, payload_len = c.payload_len,
+                 msg2_stride = c.msg2_stride;
+  const uint8_t *ephemerals = c.eph, *msg1 = c.msg1, *payload = c.payload;
+  const uint32_t* msg1_lens = c.msg1_lens;
+  uint8_t *msg2 = c.msg2, *recv_keys = c.recv, *send_keys = c.send, *hashes = c.hashes;
+  uint32_t *msg2_lens = c.msg2_lens, *ok = c.ok;
   // the work area, then the caller's arrays: in (ephemerals, msg1, lens, payload), out
-  const size_t work = noise_ix_work_bytes(n, payload_len), b_e = (size_t)n * 32, b_m1 = up16((size_t)n * msg1_stride),
+  const size_t work = noise_ix_work_bytes(c), b_e = (size_t)n * 32, b_m1 = up16((size_t)n * msg1_stride),
                b_u32 = up16((size_t)n * 4), b_pay = up16(payload_stride ? (size_t)n * payload_stride : payload_len),
                b_m2 = up16((size_t)n * msg2_stride), b_h = (size_t)n * 64;
-  if (int r = dev_scratch(h, work + b_e + b_m1 + b_u32 + b_pay + b_m2 + b_u32 + 2 * b_e + b_h + b_u32)) return r;
+  const size_t b_all = work + b_e + b_m1 + b_u32 + b_pay + b_m2 + b_u32 + 2 * b_e + b_h + b_u32;
+  if (c.lng && b_all > (size_t)GVS_AEAD_LONG_STAGE_MAX) return GVS_ERR_INVALID_ARG;  // before any allocation
+  if (!n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  if (int r = dev_scratch(h, b_all)) return r;
   uint8_t* d = h->sr_dev + work;
   uint8_t *d_e = d, *d_m1 = d_e + b_e, *d_l1 = d_m1 + b_m1, *d_pay = d_l1 + b_u32, *d_m2 = d_pay + b_pay,
           *d_l2 = d_m2 + b_m2, *d_rk = d_l2 + b_u32, *d_sk = d_rk + b_e, *d_hh = d_sk + b_e, *d_ok = d_hh + b_h;
@@ -3271,6 +3300,55 @@ int gvs_noise_ix_respond(gvs_handle* h, const uint8_t static_secret[32], const u
   if (int r = d2h(h, ok, d_ok, (size_t)n * 4)) return r;
   GVS_HIP(h, hipStreamSynchronize(h->stream));
   return bounce_done(h, GVS_OK);
+}
+
+int gvs_noise_ix_respond_device(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
+                                uint32_t prologue_len, const void* d_ephemerals, const void* d_msg1,
+                                uint32_t msg1_stride, const uint32_t* d_msg1_lens, const void* d_payload,
+                                uint32_t payload_stride, uint32_t payload_len, uint32_t n, void* d_msg2,
+                                uint32_t msg2_stride, uint32_t* d_msg2_lens, void* d_recv_keys,
+                                void* d_send_keys, void* d_hashes, uint32_t* d_ok) {
+  return noise_ix_device(h, NoiseIxCall{static_secret, prologue, prologue_len, (const uint8_t*)d_ephemerals,
+                                        (const uint8_t*)d_msg1, msg1_stride, d_msg1_lens, (const uint8_t*)d_payload,
+                                        payload_stride, payload_len, n, (uint8_t*)d_msg2, msg2_stride, d_msg2_lens,
+                                        (uint8_t*)d_recv_keys, (uint8_t*)d_send_keys, (uint8_t*)d_hashes, d_ok,
+                                        false});
+}
+
+int gvs_noise_ix_respond(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
+                         uint32_t prologue_len, const uint8_t* ephemerals, const uint8_t* msg1,
+                         uint32_t msg1_stride, const uint32_t* msg1_lens, const uint8_t* payload,
+                         uint32_t payload_stride, uint32_t payload_len, uint32_t n, uint8_t* msg2,
+                         uint32_t msg2_stride, uint32_t* msg2_lens, uint8_t* recv_keys, uint8_t* send_keys,
+                         uint8_t* hashes, uint32_t* ok) {
+  return noise_ix_host(h, NoiseIxCall{static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride, msg1_lens,
+                                      payload, payload_stride, payload_len, n, msg2, msg2_stride, msg2_lens,
+                                      recv_keys, send_keys, hashes, ok, false});
+}
+
+// the long forms: the same argument lists, k_aead_long, k_noise_ix_tail and their limits
+int gvs_noise_ix_respond_long_device(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
+                                     uint32_t prologue_len, const void* d_ephemerals, const void* d_msg1,
+                                     uint32_t msg1_stride, const uint32_t* d_msg1_lens, const void* d_payload,
+                                     uint32_t payload_stride, uint32_t payload_len, uint32_t n, void* d_msg2,
+                                     uint32_t msg2_stride, uint32_t* d_msg2_lens, void* d_recv_keys,
+                                     void* d_send_keys, void* d_hashes, uint32_t* d_ok) {
+  return noise_ix_device(h, NoiseIxCall{static_secret, prologue, prologue_len, (const uint8_t*)d_ephemerals,
+                                        (const uint8_t*)d_msg1, msg1_stride, d_msg1_lens, (const uint8_t*)d_payload,
+                                        payload_stride, payload_len, n, (uint8_t*)d_msg2, msg2_stride, d_msg2_lens,
+                                        (uint8_t*)d_recv_keys, (uint8_t*)d_send_keys, (uint8_t*)d_hashes, d_ok,
+                                        true});
+}
+
+int gvs_noise_ix_respond_long(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
+                              uint32_t prologue_len, const uint8_t* ephemerals, const uint8_t* msg1,
+                              uint32_t msg1_stride, const uint32_t* msg1_lens, const uint8_t* payload,
+                              uint32_t payload_stride, uint32_t payload_len, uint32_t n, uint8_t* msg2,
+                              uint32_t msg2_stride, uint32_t* msg2_lens, uint8_t* recv_keys, uint8_t* send_keys,
+                              uint8_t* hashes, uint32_t* ok) {
+  return noise_ix_host(h, NoiseIxCall{static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride, msg1_lens,
+                                      payload, payload_stride, payload_len, n, msg2, msg2_stride, msg2_lens,
+                                      recv_keys, send_keys, hashes, ok, true});
 }
 
 // ---------------------------------------------------- channel cipher alone

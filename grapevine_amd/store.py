@@ -42,6 +42,7 @@ EXPORTED = (
     "gvs_process_wire_batch_channel", "gvs_process_wire_batch_channel_device",
     "gvs_x25519", "gvs_x25519_device", "gvs_noise_hkdf", "gvs_noise_hkdf_device",
     "gvs_noise_ix_respond", "gvs_noise_ix_respond_device",
+    "gvs_noise_ix_respond_long", "gvs_noise_ix_respond_long_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -110,6 +111,8 @@ def load_library(path=None):
     lib.gvs_noise_hkdf_device.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, u32]
     lib.gvs_noise_ix_respond.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
     lib.gvs_noise_ix_respond_device.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
+    lib.gvs_noise_ix_respond_long.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
+    lib.gvs_noise_ix_respond_long_device.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
     lib.gvs_wire_decode_device.argtypes =[vp, vp, u32, vp, u32, vp, vp, vp, vp]
     lib.gvs_wire_encode_device.argtypes = [vp, vp, u32, vp, u32, vp]
     lib.gvs_process_batches.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(u32)]
@@ -590,6 +593,23 @@ class ObliviousStore:
         (n, 32), hashes (n, 64), (n,) bool, the (n, stride) message-2 slab).  A
         handshake that fails is b"" with zero keys and hash.  The form on
         torch tensors is `noise_ix_respond_device`."""
+        return self._noise_ix_respond(self.lib.gvs_noise_ix_respond, 1, static_secret, ephemerals, msg1,
+                                      payload, prologue, msg2_stride)
+
+    def noise_ix_respond_long(self, static_secret, ephemerals, msg1, payload=b"", prologue=b"",
+                              msg2_stride=None):
+        """noise_ix_respond with a payload of up to abi.NOISE_PAYLOAD2_LONG_MAX
+        bytes inside message 2 (gvs_noise_ix_respond_long): the same arguments
+        and results; msg2_stride is a multiple of 16 (default: 96 + the
+        payload's length, rounded up).  The form on torch tensors is
+        `noise_ix_respond_long_device`."""
+        return self._noise_ix_respond(self.lib.gvs_noise_ix_respond_long, 16, static_secret, ephemerals, msg1,
+                                      payload, prologue, msg2_stride)
+
+    def _noise_ix_respond(self, fn, align, static_secret, ephemerals, msg1, payload, prologue, msg2_stride):
+        """The host forms: payload rows and the default message-2 stride are
+        rounded up to `align` bytes."""
+        up = lambda v: -(-v // align) * align
         n = len(msg1)
         eph = np.ascontiguousarray(ephemerals, np.uint8).reshape(n, 32)
         slab, lens, stride = self._wire_slab(msg1, max([len(m) for m in msg1] + [64]))
@@ -598,33 +618,40 @@ class ObliviousStore:
         p2 = len(pays[0]) if pays else 0
         if any(len(p) != p2 for p in pays) or (not one and len(pays) != n):
             raise ValueError("noise_ix_respond: one payload length per call")
-        pay = np.frombuffer(b"".join(pays), np.uint8) if p2 else None
-        m2s = msg2_stride if msg2_stride is not None else 96 + p2
+        pay = np.frombuffer(b"".join(p.ljust(up(p2), b"\0") for p in pays), np.uint8) if p2 else None
+        m2s = msg2_stride if msg2_stride is not None else up(96 + p2)
         msg2 = np.zeros((n, max(m2s, 1)), np.uint8)
         m2l, ok = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         rk, sk, hh = np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros((n, 64), np.uint8)
-        self._check(self.lib.gvs_noise_ix_respond(
+        self._check(fn(
             self.h, bytes(static_secret), bytes(prologue), len(prologue), eph.ctypes.data, slab.ctypes.data,
-            stride, lens.ctypes.data, pay.ctypes.data if pay is not None else None, 0 if one else p2, p2, n,
+            stride, lens.ctypes.data, pay.ctypes.data if pay is not None else None, 0 if one else up(p2), p2, n,
             msg2.ctypes.data, m2s, m2l.ctypes.data, rk.ctypes.data, sk.ctypes.data, hh.ctypes.data,
             ok.ctypes.data))
         return [msg2[k, :m2l[k]].tobytes() for k in range(n)], rk, sk, hh, ok.astype(bool), msg2
 
     def noise_ix_respond_device(self, static_secret, ephemerals, msg1, msg1_lens, payload, payload_len,
-                                msg2, msg2_lens, recv_keys, send_keys, hashes, ok, prologue=b""):
+                                msg2, msg2_lens, recv_keys, send_keys, hashes, ok, prologue=b"", long=False):
         """gvs_noise_ix_respond_device on torch CUDA tensors: ephemerals
         (n, >= 32 contiguous 32), msg1 (n, stride) uint8, msg1_lens (n,) int32,
         payload (n, stride) uint8, a 1-D tensor (one payload for all) or None,
         and the outputs msg2 (n, stride) uint8, msg2_lens (n,) int32,
         recv_keys / send_keys (n, 32), hashes (n, 64) or None, ok (n,) int32,
-        all written in place.  The caller synchronises its own streams first."""
+        all written in place.  The caller synchronises its own streams first.
+        long: gvs_noise_ix_respond_long_device, whose payload and msg2 rows are
+        16-byte aligned, with strides that are multiples of 16."""
         n = msg1.shape[0]
         ptr = lambda t: t.data_ptr() if t is not None else None
         pstride = 0 if payload is None or payload.dim() == 1 else payload.stride(0)
-        self._check(self.lib.gvs_noise_ix_respond_device(
+        fn = self.lib.gvs_noise_ix_respond_long_device if long else self.lib.gvs_noise_ix_respond_device
+        self._check(fn(
             self.h, bytes(static_secret), bytes(prologue), len(prologue), ptr(ephemerals), ptr(msg1),
             msg1.stride(0), ptr(msg1_lens), ptr(payload), pstride, payload_len, n, ptr(msg2), msg2.stride(0),
             ptr(msg2_lens), ptr(recv_keys), ptr(send_keys), ptr(hashes), ptr(ok)))
+
+    def noise_ix_respond_long_device(self, *args, **kw):
+        """noise_ix_respond_device(..., long=True)."""
+        self.noise_ix_respond_device(*args, long=True, **kw)
 
     def access(self, req):
         out = self.process_batch(np.asarray([req], dtype=abi.REQUEST_DTYPE) if not isinstance(req, np.ndarray) else req.reshape(1))

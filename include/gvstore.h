@@ -572,6 +572,40 @@ int gvs_noise_ix_respond_device(gvs_handle *h, const uint8_t static_secret[32],
                                 void *d_recv_keys, void *d_send_keys, void *d_hashes,
                                 uint32_t *d_ok);
 
+/* The same handshake with a message-2 payload of up to
+ * GVS_NOISE_PAYLOAD2_LONG_MAX bytes (message 2 = 96 + payload_len <= 65 535,
+ * Noise's limit), for attestation evidence that a standard initiator expects
+ * inside message 2: the argument lists, the outputs and the
+ * per-handshake failures of gvs_noise_ix_respond, and its bytes where both
+ * accept the payload.  msg2_stride is a multiple of 16, at least 96 +
+ * payload_len and at most 65 536; payload_stride is 0 (one payload for all) or
+ * a multiple of 16 that holds payload_len; the device form wants d_msg2 and
+ * d_payload 16-byte aligned (it reads the caller's payload rows in place).
+ * Anything else is GVS_ERR_INVALID_ARG, and so is a call whose work area
+ * (n sealed payloads, and n copies of a payload that all share) plus, in the
+ * host form, its staging would pass GVS_AEAD_LONG_STAGE_MAX bytes, before
+ * anything is allocated.  The transcript hash over the sealed payload is one
+ * serial SHA-512 chain per handshake: a call takes about 128-byte blocks of
+ * payload x the per-block time of a lane, whatever n is, until the device is
+ * full. */
+#define GVS_NOISE_PAYLOAD2_LONG_MAX 65439
+int gvs_noise_ix_respond_long(gvs_handle *h, const uint8_t static_secret[32],
+                              const uint8_t *prologue, uint32_t prologue_len,
+                              const uint8_t *ephemerals, const uint8_t *msg1, uint32_t msg1_stride,
+                              const uint32_t *msg1_lens, const uint8_t *payload,
+                              uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                              uint8_t *msg2, uint32_t msg2_stride, uint32_t *msg2_lens,
+                              uint8_t *recv_keys, uint8_t *send_keys, uint8_t *hashes, uint32_t *ok);
+int gvs_noise_ix_respond_long_device(gvs_handle *h, const uint8_t static_secret[32],
+                                     const uint8_t *prologue, uint32_t prologue_len,
+                                     const void *d_ephemerals, const void *d_msg1,
+                                     uint32_t msg1_stride, const uint32_t *d_msg1_lens,
+                                     const void *d_payload, uint32_t payload_stride,
+                                     uint32_t payload_len, uint32_t n, void *d_msg2,
+                                     uint32_t msg2_stride, uint32_t *d_msg2_lens,
+                                     void *d_recv_keys, void *d_send_keys, void *d_hashes,
+                                     uint32_t *d_ok);
+
 /* Message expiry (README.md:86-99: the untrusted host supplies the time and
  * the expiry period).  From the next batch on, messages whose timestamp is
  * < cutoff expire: each batch's message pass records up to X of them (fixed
