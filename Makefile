@@ -19,8 +19,9 @@ AEADLONGHOST := tests/libaeadlonghost.so
 XHOST := tests/libxhost.so
 NHOST := tests/libnhost.so
 NLONGHOST := tests/libnlonghost.so
+CPHOST := tests/libchachapolyhost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -39,7 +40,7 @@ $(EDHOST): tests/ed_host.cpp grapevine_amd/csrc/gvs_ed25519.h grapevine_amd/csrc
 
 # the device challenge stream (ChaCha20 block, draw selection) built for the
 # CPU (tests/test_chacha_host.py)
-$(CHACHAHOST): tests/chacha_host.cpp grapevine_amd/csrc/gvs_chacha.h
+$(CHACHAHOST): tests/chacha_host.cpp grapevine_amd/csrc/gvs_chacha.h grapevine_amd/csrc/gvs_chacha_rounds.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/chacha_host.cpp
 
 # the device channel cipher's primitives (AES-256, GF(2^128), the serial
@@ -68,11 +69,17 @@ $(NHOST): tests/noise_host.cpp tests/aead_host.cpp $(wildcard grapevine_amd/csrc
 $(NLONGHOST): tests/noise_long_host.cpp tests/noise_host.cpp tests/aead_host.cpp $(wildcard grapevine_amd/csrc/*.h)
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/noise_long_host.cpp
 
+# the second channel cipher's primitives (the RFC 8439 block function,
+# Poly1305 over 26-bit limbs, the serial ChaCha20-Poly1305) built for the CPU
+# (tests/test_chachapoly.py)
+$(CPHOST): tests/chachapoly_host.cpp grapevine_amd/csrc/gvs_chachapoly.h grapevine_amd/csrc/gvs_chacha_rounds.h grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/chachapoly_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

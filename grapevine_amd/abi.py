@@ -123,6 +123,18 @@ def noise_iv(counter):
     four zero bytes, then the counter as 64 bits big-endian."""
     return bytes(4) + int(counter).to_bytes(8, "big")
 
+
+# the channel's cipher (GVS_CIPHER_*): which AEAD a channel call and a
+# handshake use, and with it the Noise suite's name
+CIPHER_AESGCM, CIPHER_CHACHAPOLY = 0, 1
+
+
+def noise_nonce_chachapoly(counter):
+    """Noise's ChaChaPoly nonce for message number `counter` of a cipher
+    state: four zero bytes, then the counter as 64 bits little-endian
+    (`noise_iv`, AESGCM's, is big-endian)."""
+    return bytes(4) + int(counter).to_bytes(8, "little")
+
 COMM_ID_BYTES = 128
 # GVS_FLAG_AUTH_STORAGE: AES-CTR sealed tables; rows of tables 0, 1, 2 and
 # 0x100 carry an AES header and the NH/L3 row hash, the map directory (table 3)

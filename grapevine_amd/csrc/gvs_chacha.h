@@ -23,24 +23,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gvs_chacha_rounds.h"  // GVS_CC_QR, GVS_CC_DR
+
 namespace gvs {
 
 #define GVS_CC_FN __host__ __device__ __forceinline__
 
 constexpr uint32_t kChallengeThreads = 256;
-
-#define GVS_CC_QR(a, b, c, d)                \
-  a += b; d = __builtin_rotateleft32(d ^ a, 16); \
-  c += d; b = __builtin_rotateleft32(b ^ c, 12); \
-  a += b; d = __builtin_rotateleft32(d ^ a, 8);  \
-  c += d; b = __builtin_rotateleft32(b ^ c, 7);
-
-// two rounds: the four columns, then the four diagonals
-#define GVS_CC_DR                                                 \
-  GVS_CC_QR(x0, x4, x8, x12) GVS_CC_QR(x1, x5, x9, x13)           \
-  GVS_CC_QR(x2, x6, x10, x14) GVS_CC_QR(x3, x7, x11, x15)         \
-  GVS_CC_QR(x0, x5, x10, x15) GVS_CC_QR(x1, x6, x11, x12)         \
-  GVS_CC_QR(x2, x7, x8, x13) GVS_CC_QR(x3, x4, x9, x14)
 
 // out = the 64-byte ChaCha20 block (16 little-endian words) of `key` at block
 // `counter` of stream `stream`
@@ -72,9 +61,6 @@ GVS_CC_FN void chacha20_block(const uint32_t key[8], uint64_t counter, uint64_t 
   out[14] = x14 + n2;
   out[15] = x15 + n3;
 }
-
-#undef GVS_CC_DR
-#undef GVS_CC_QR
 
 // out = draw number `draw` (32 bytes, 8 little-endian words) of
 // ChaCha20Rng(key): the low or the high half of block draw >> 1, taken with

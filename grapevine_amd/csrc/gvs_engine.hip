@@ -38,6 +38,7 @@
 #include "gvs_chacha.h"
 #include "gvs_aead.h"
 #include "gvs_aead_long.h"
+#include "gvs_chachapoly.h"
 #include "gvs_noise_long.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
@@ -2526,6 +2527,7 @@ struct ChanKeys {
   const void* open_ivs = nullptr;
   const void* seal_keys = nullptr;
   const void* seal_ivs = nullptr;
+  uint32_t cipher = GVS_CIPHER_AESGCM;  // or GVS_CIPHER_CHACHAPOLY: k_chachapoly (gvs_chachapoly.h) in k_aead's place
   bool all() const { return open_keys && open_ivs && seal_keys && seal_ivs; }
 };
 
@@ -2551,6 +2553,27 @@ static void enqueue_aead(gvs_handle* h, bool seal, AeadArgs a) {
     hipLaunchKernelGGL(k_aead<true>, grid, block, 0, h->stream, a);
   else
     hipLaunchKernelGGL(k_aead<false>, grid, block, 0, h->stream, a);
+}
+
+// ChaCha20-Poly1305 on the same arguments (gvs_chachapoly.h): 16 messages per workgroup
+static void enqueue_chachapoly(gvs_handle* h, bool seal, AeadArgs a) {
+  if (!a.n) return;
+  const dim3 grid((a.n + kCpMsgs - 1) / kCpMsgs), block(kCpThreads);
+  if (seal)
+    hipLaunchKernelGGL(k_chachapoly<true>, grid, block, 0, h->stream, a);
+  else
+    hipLaunchKernelGGL(k_chachapoly<false>, grid, block, 0, h->stream, a);
+}
+
+// a channel call's or a handshake's cipher, and its stage mark
+static void enqueue_cipher(gvs_handle* h, uint32_t cipher, bool seal, const AeadArgs& a) {
+  if (cipher == GVS_CIPHER_CHACHAPOLY) {
+    enqueue_chachapoly(h, seal, a);
+    mark(h, seal ? "chachapoly_seal" : "chachapoly_open");
+  } else {
+    enqueue_aead(h, seal, a);
+    mark(h, seal ? "aead_seal" : "aead_open");
+  }
 }
 
 // the long form (gvs_aead_long.h): one workgroup per message
@@ -2586,8 +2609,7 @@ static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const
     a.out_stride = in_stride;
     a.out_lens = w.pt_lens;
     a.ok = w.opened;
-    enqueue_aead(h, false, a);
-    mark(h, "aead_open");
+    enqueue_cipher(h, ch->cipher, false, a);
     d_in = w.pt_in;
     d_in_lens = w.pt_lens;
   }
@@ -2630,8 +2652,7 @@ static int wire_batch(gvs_handle* h, const void* d_in, uint32_t in_stride, const
     a.opened = w.opened;
     a.status = status;
     a.bad_status = GVS_WIRE_BAD_CHANNEL_TAG;
-    enqueue_aead(h, true, a);
-    mark(h, "aead_seal");
+    enqueue_cipher(h, ch->cipher, true, a);
   }
   GVS_HIP(h, hipGetLastError());
   return GVS_OK;
@@ -2666,14 +2687,14 @@ static int wire_batch_device(gvs_handle* h, const void* d_in, uint32_t in_stride
       (n && (!d_in || !d_in_lens || !d_times || !d_out || !d_out_lens)) || !ci.ok() ||
       !aligned16(ci.seeds) || !aligned16(ci.challenges_out))
     return GVS_ERR_INVALID_ARG;
-  if (ch && (!channel_strides_ok(in_stride, out_stride) || (n && !ch->all()) || !aligned16(d_in) ||
+  if (ch && (ch->cipher > GVS_CIPHER_CHACHAPOLY || !channel_strides_ok(in_stride, out_stride) || (n && !ch->all()) || !aligned16(d_in) ||
              !aligned16(d_out) || !aligned16(ch->open_keys) || !aligned16(ch->seal_keys) ||
              ((uintptr_t)ch->open_ivs & 3u) || ((uintptr_t)ch->seal_ivs & 3u)))
     return GVS_ERR_INVALID_ARG;
   if (h->poisoned) return GVS_ERR_INTEGRITY;
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
-  if (ch)
+  if (ch && ch->cipher == GVS_CIPHER_AESGCM)
     if (int r = aead_init(h)) return r;
   ChalSrc cs{const_cast<void*>(ci.challenges), nullptr, nullptr};
   if (ci.seeded()) {
@@ -2721,18 +2742,18 @@ static int wire_batch_host(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
                            uint8_t* sigs, uint32_t* decode_status, const ChanKeys* ch = nullptr) {
   if (!h || h->kind != 0 || !wire_strides_ok(in_stride, out_stride) || n > max_submit(h) ||
       (n && (!in || !in_lens || !times || !out || !out_lens)) || !ci.ok() ||
-      (ch && (!channel_strides_ok(in_stride, out_stride) || (n && !ch->all()))))
+      (ch && (ch->cipher > GVS_CIPHER_CHACHAPOLY || !channel_strides_ok(in_stride, out_stride) || (n && !ch->all()))))
     return GVS_ERR_INVALID_ARG;
   if (h->poisoned) return GVS_ERR_INTEGRITY;
   if (int r = check_epoch(h)) return r;
   GVS_HIP(h, hipSetDevice(h->device));
-  if (ch)
+  if (ch && ch->cipher == GVS_CIPHER_AESGCM)
     if (int r = aead_init(h)) return r;
   if (int rc = wire_stage_init(h, true, ci.seeded(), ch != nullptr)) return rc;
   WireStage& w = h->wire;
   if (int r = bounce_begin(h)) return r;
   ChanKeys dch;  // the ciphers' keys and IVs on the device
-  if (ch) dch = ChanKeys{w.ckeys[0], w.civs[0], w.ckeys[1], w.civs[1]};
+  if (ch) dch = ChanKeys{w.ckeys[0], w.civs[0], w.ckeys[1], w.civs[1], ch->cipher};
   if (n && ch) {
     if (int r = h2d(h, w.ckeys[0], ch->open_keys, (size_t)n * 32)) return r;
     if (int r = h2d(h, w.civs[0], ch->open_ivs, (size_t)n * kAeadIv)) return r;
@@ -2793,6 +2814,22 @@ int gvs_process_wire_batch_seeded(gvs_handle* h, const uint8_t* in, uint32_t in_
                          decode_status);
 }
 
+int gvs_process_wire_batch_channel_cipher(gvs_handle* h, uint32_t cipher, const uint8_t* in, uint32_t in_stride,
+                                          const uint32_t* in_lens, uint32_t n, const uint64_t* times,
+                                          const uint8_t* seeds, const uint64_t* draws,
+                                          const uint8_t* open_keys, const uint8_t* open_ivs,
+                                          const uint8_t* seal_keys, const uint8_t* seal_ivs, uint8_t* out,
+                                          uint32_t out_stride, uint32_t* out_lens, uint8_t* sigs,
+                                          uint32_t* decode_status, uint8_t* challenges_out) {
+  ChalIn ci;
+  ci.seeds = seeds;
+  ci.draws = draws;
+  ci.challenges_out = challenges_out;
+  const ChanKeys ch{open_keys, open_ivs, seal_keys, seal_ivs, cipher};
+  return wire_batch_host(h, in, in_stride, in_lens, n, times, ci, out, out_stride, out_lens, sigs,
+                         decode_status, &ch);
+}
+
 int gvs_process_wire_batch_channel(gvs_handle* h, const uint8_t* in, uint32_t in_stride,
                                    const uint32_t* in_lens, uint32_t n, const uint64_t* times,
                                    const uint8_t* seeds, const uint64_t* draws,
@@ -2800,13 +2837,26 @@ int gvs_process_wire_batch_channel(gvs_handle* h, const uint8_t* in, uint32_t in
                                    const uint8_t* seal_keys, const uint8_t* seal_ivs, uint8_t* out,
                                    uint32_t out_stride, uint32_t* out_lens, uint8_t* sigs,
                                    uint32_t* decode_status, uint8_t* challenges_out) {
+  return gvs_process_wire_batch_channel_cipher(h, GVS_CIPHER_AESGCM, in, in_stride, in_lens, n, times, seeds, draws,
+                                               open_keys, open_ivs, seal_keys, seal_ivs, out, out_stride, out_lens,
+                                               sigs, decode_status, challenges_out);
+}
+
+int gvs_process_wire_batch_channel_cipher_device(gvs_handle* h, uint32_t cipher, const void* d_in,
+                                                 uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n,
+                                                 const uint64_t* d_times, const void* d_seeds,
+                                                 const uint64_t* d_draws, const void* d_open_keys,
+                                                 const void* d_open_ivs, const void* d_seal_keys,
+                                                 const void* d_seal_ivs, void* d_out, uint32_t out_stride,
+                                                 uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status,
+                                                 void* d_challenges_out) {
   ChalIn ci;
-  ci.seeds = seeds;
-  ci.draws = draws;
-  ci.challenges_out = challenges_out;
-  const ChanKeys ch{open_keys, open_ivs, seal_keys, seal_ivs};
-  return wire_batch_host(h, in, in_stride, in_lens, n, times, ci, out, out_stride, out_lens, sigs,
-                         decode_status, &ch);
+  ci.seeds = d_seeds;
+  ci.draws = d_draws;
+  ci.challenges_out = d_challenges_out;
+  const ChanKeys ch{d_open_keys, d_open_ivs, d_seal_keys, d_seal_ivs, cipher};
+  return wire_batch_device(h, d_in, in_stride, d_in_lens, n, d_times, ci, d_out, out_stride,
+                           d_out_lens, d_sigs, d_status, &ch);
 }
 
 int gvs_process_wire_batch_channel_device(gvs_handle* h, const void* d_in, uint32_t in_stride,
@@ -2817,13 +2867,10 @@ int gvs_process_wire_batch_channel_device(gvs_handle* h, const void* d_in, uint3
                                           const void* d_seal_ivs, void* d_out, uint32_t out_stride,
                                           uint32_t* d_out_lens, void* d_sigs, uint32_t* d_status,
                                           void* d_challenges_out) {
-  ChalIn ci;
-  ci.seeds = d_seeds;
-  ci.draws = d_draws;
-  ci.challenges_out = d_challenges_out;
-  const ChanKeys ch{d_open_keys, d_open_ivs, d_seal_keys, d_seal_ivs};
-  return wire_batch_device(h, d_in, in_stride, d_in_lens, n, d_times, ci, d_out, out_stride,
-                           d_out_lens, d_sigs, d_status, &ch);
+  return gvs_process_wire_batch_channel_cipher_device(h, GVS_CIPHER_AESGCM, d_in, in_stride, d_in_lens, n, d_times,
+                                                      d_seeds, d_draws, d_open_keys, d_open_ivs, d_seal_keys,
+                                                      d_seal_ivs, d_out, out_stride, d_out_lens, d_sigs, d_status,
+                                                      d_challenges_out);
 }
 
 static int wire_pipe_seeded_init(gvs_handle* h) {
@@ -3124,10 +3171,12 @@ struct NoiseIxCall {
   uint8_t *recv, *send, *hashes;
   uint32_t* ok;
   bool lng = false;  // the long calls: k_aead_long and k_noise_ix_tail (gvs_noise_long.h), with their limits
+  uint32_t cipher = GVS_CIPHER_AESGCM;  // GVS_CIPHER_CHACHAPOLY: the other suite (short calls only)
 };
 
 static bool noise_ix_call_ok(gvs_handle* h, const NoiseIxCall& c) {
-  return h && c.static_secret && c.prologue_len <= sr::kNxPrologueMax && (!c.prologue_len || c.prologue) &&
+  return h && c.cipher <= GVS_CIPHER_CHACHAPOLY && !(c.lng && c.cipher != GVS_CIPHER_AESGCM) && c.static_secret &&
+         c.prologue_len <= sr::kNxPrologueMax && (!c.prologue_len || c.prologue) &&
          c.payload_len <= (c.lng ? sr::kNxPayload2LongMax : kAeadTextMax) && (!c.payload_len || c.payload) &&
          (!c.payload_stride || c.payload_stride >= c.payload_len) && c.msg1_stride >= 64 &&
          (uint64_t)c.msg2_stride >= (uint64_t)sr::kNxMsg2Fixed + c.payload_len && c.n <= max_submit(h) &&
@@ -3162,7 +3211,9 @@ static size_t noise_ix_work_bytes(const NoiseIxCall& c) {
 // k_noise_ix_tail instead.  c's arrays are device memory; `work` holds
 // noise_ix_work_bytes, 16-byte aligned.
 static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
-  if (int r = aead_init(h)) return r;
+  const bool cp = c.cipher == GVS_CIPHER_CHACHAPOLY;
+  if (!cp)
+    if (int r = aead_init(h)) return r;
   const uint32_t n = c.n, p2 = c.payload_len, t2 = noise_ix_text2(c), c2 = noise_ix_ct2(c);
   const size_t x = 4 * (size_t)n + 1;
   uint8_t* p = work;
@@ -3225,10 +3276,12 @@ static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   }
   enqueue_x25519(h, sr::XArgs{xsc, 32, xpt, 32, (uint32_t)x, xout, 32, xok});
   mark(h, "x25519");
-  hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxA>, grid, block, 0, h->stream, a);
+  if (cp)
+    hipLaunchKernelGGL(sr::k_noise_ix_a_chachapoly, grid, block, 0, h->stream, a);
+  else
+    hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxA>, grid, block, 0, h->stream, a);
   mark(h, "noise_a");
-  enqueue_aead(h, true, s1);
-  mark(h, "aead_seal");
+  enqueue_cipher(h, c.cipher, true, s1);
   hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxB>, grid, block, 0, h->stream, a);
   mark(h, "noise_b");
   if (c.lng) {
@@ -3238,8 +3291,7 @@ static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
                        h->stream, a);
     mark(h, "noise_tail");
   } else {
-    enqueue_aead(h, true, s2);
-    mark(h, "aead_seal");
+    enqueue_cipher(h, c.cipher, true, s2);
     hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxC>, grid, block, 0, h->stream, a);
     mark(h, "noise_c");
   }
@@ -3326,6 +3378,32 @@ int gvs_noise_ix_respond(gvs_handle* h, const uint8_t static_secret[32], const u
                                       recv_keys, send_keys, hashes, ok, false});
 }
 
+// the short responder with the suite chosen: GVS_CIPHER_CHACHAPOLY is
+// Noise_IX_25519_ChaChaPoly_SHA512 (phase A's other name, k_chachapoly<true> for both seals)
+int gvs_noise_ix_respond_cipher_device(gvs_handle* h, uint32_t cipher, const uint8_t static_secret[32],
+                                       const uint8_t* prologue, uint32_t prologue_len, const void* d_ephemerals,
+                                       const void* d_msg1, uint32_t msg1_stride, const uint32_t* d_msg1_lens,
+                                       const void* d_payload, uint32_t payload_stride, uint32_t payload_len,
+                                       uint32_t n, void* d_msg2, uint32_t msg2_stride, uint32_t* d_msg2_lens,
+                                       void* d_recv_keys, void* d_send_keys, void* d_hashes, uint32_t* d_ok) {
+  return noise_ix_device(h, NoiseIxCall{static_secret, prologue, prologue_len, (const uint8_t*)d_ephemerals,
+                                        (const uint8_t*)d_msg1, msg1_stride, d_msg1_lens, (const uint8_t*)d_payload,
+                                        payload_stride, payload_len, n, (uint8_t*)d_msg2, msg2_stride, d_msg2_lens,
+                                        (uint8_t*)d_recv_keys, (uint8_t*)d_send_keys, (uint8_t*)d_hashes, d_ok,
+                                        false, cipher});
+}
+
+int gvs_noise_ix_respond_cipher(gvs_handle* h, uint32_t cipher, const uint8_t static_secret[32],
+                                const uint8_t* prologue, uint32_t prologue_len, const uint8_t* ephemerals,
+                                const uint8_t* msg1, uint32_t msg1_stride, const uint32_t* msg1_lens,
+                                const uint8_t* payload, uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                                uint8_t* msg2, uint32_t msg2_stride, uint32_t* msg2_lens, uint8_t* recv_keys,
+                                uint8_t* send_keys, uint8_t* hashes, uint32_t* ok) {
+  return noise_ix_host(h, NoiseIxCall{static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride, msg1_lens,
+                                      payload, payload_stride, payload_len, n, msg2, msg2_stride, msg2_lens,
+                                      recv_keys, send_keys, hashes, ok, false, cipher});
+}
+
 // the long forms: the same argument lists, k_aead_long, k_noise_ix_tail and their limits
 int gvs_noise_ix_respond_long_device(gvs_handle* h, const uint8_t static_secret[32], const uint8_t* prologue,
                                      uint32_t prologue_len, const void* d_ephemerals, const void* d_msg1,
@@ -3380,12 +3458,13 @@ static bool aead_call_ok(gvs_handle* h, const AeadCall& c, bool seal, bool lng) 
          (!c.n || (c.keys && c.ivs && c.in && c.in_lens && c.out && c.out_lens && (seal || c.ok)));
 }
 
-static int aead_device(gvs_handle* h, const AeadCall& c, bool seal, bool lng) {
+static int aead_device(gvs_handle* h, const AeadCall& c, bool seal, bool lng, uint32_t cipher = GVS_CIPHER_AESGCM) {
   if (!aead_call_ok(h, c, seal, lng) || !aligned16(c.keys) || !aligned16(c.aad) || !aligned16(c.in) ||
       !aligned16(c.out) || ((uintptr_t)c.ivs & 3u))
     return GVS_ERR_INVALID_ARG;
   GVS_HIP(h, hipSetDevice(h->device));
-  if (int r = aead_init(h)) return r;
+  if (cipher == GVS_CIPHER_AESGCM)
+    if (int r = aead_init(h)) return r;
   AeadArgs a{};
   a.keys = (const uint4*)c.keys;
   a.ivs = (const uint32_t*)c.ivs;
@@ -3401,12 +3480,14 @@ static int aead_device(gvs_handle* h, const AeadCall& c, bool seal, bool lng) {
   a.out_lens = c.out_lens;
   a.ok = c.ok;
   if (lng) return launch_sync(h, seal ? "aead_seal_long" : "aead_open_long", [&] { enqueue_aead_long(h, seal, a); });
+  if (cipher == GVS_CIPHER_CHACHAPOLY)
+    return launch_sync(h, seal ? "chachapoly_seal" : "chachapoly_open", [&] { enqueue_chachapoly(h, seal, a); });
   return launch_sync(h, seal ? "aead_seal" : "aead_open", [&] { enqueue_aead(h, seal, a); });
 }
 
 // the host forms: the lengths are checked here (the device forms fail such a
 // message alone), then everything goes through the device scratch
-static int aead_host(gvs_handle* h, const AeadCall& c, bool seal, bool lng) {
+static int aead_host(gvs_handle* h, const AeadCall& c, bool seal, bool lng, uint32_t cipher = GVS_CIPHER_AESGCM) {
   if (!aead_call_ok(h, c, seal, lng)) return GVS_ERR_INVALID_ARG;
   const uint32_t text_max = lng ? kAeadLongTextMax : kAeadTextMax;
   for (uint32_t k = 0; k < c.n; ++k) {
@@ -3438,7 +3519,7 @@ static int aead_host(gvs_handle* h, const AeadCall& c, bool seal, bool lng) {
   if (int r = h2d(h, d_u32[1], c.in_lens, n * 4)) return r;
   const AeadCall dc{d, d_iv, c.aad ? d_aad : nullptr, c.aad_stride, d_u32[0], d_in, c.in_stride, d_u32[1],
                     c.n, d_out, c.out_stride, d_u32[2], d_u32[3]};
-  if (int r = aead_device(h, dc, seal, lng)) return bounce_done(h, r);
+  if (int r = aead_device(h, dc, seal, lng, cipher)) return bounce_done(h, r);
   if (int r = d2h(h, c.out, d_out, b_out)) return r;
   if (int r = d2h(h, c.out_lens, d_u32[2], n * 4)) return r;
   if (c.ok)
@@ -3477,6 +3558,39 @@ int gvs_aead_seal(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, const 
                   uint32_t* out_lens) {
   return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
                                out_stride, out_lens, nullptr}, true, false);
+}
+
+// ChaCha20-Poly1305 (gvs_chachapoly.h): the argument lists, limits and failures of the calls above
+int gvs_chachapoly_open_device(gvs_handle* h, const void* d_keys, const void* d_nonces, const void* d_aad,
+                               uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                               uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                               uint32_t out_stride, uint32_t* d_out_lens, uint32_t* d_ok) {
+  return aead_device(h, AeadCall{d_keys, d_nonces, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, d_ok}, false, false, GVS_CIPHER_CHACHAPOLY);
+}
+
+int gvs_chachapoly_seal_device(gvs_handle* h, const void* d_keys, const void* d_nonces, const void* d_aad,
+                               uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                               uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                               uint32_t out_stride, uint32_t* d_out_lens) {
+  return aead_device(h, AeadCall{d_keys, d_nonces, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, nullptr}, true, false, GVS_CIPHER_CHACHAPOLY);
+}
+
+int gvs_chachapoly_open(gvs_handle* h, const uint8_t* keys, const uint8_t* nonces, const uint8_t* aad,
+                        uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                        const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                        uint32_t* out_lens, uint32_t* ok) {
+  return aead_host(h, AeadCall{keys, nonces, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, ok}, false, false, GVS_CIPHER_CHACHAPOLY);
+}
+
+int gvs_chachapoly_seal(gvs_handle* h, const uint8_t* keys, const uint8_t* nonces, const uint8_t* aad,
+                        uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                        const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                        uint32_t* out_lens) {
+  return aead_host(h, AeadCall{keys, nonces, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, nullptr}, true, false, GVS_CIPHER_CHACHAPOLY);
 }
 
 // the long forms: the same argument lists, k_aead_long and its limits

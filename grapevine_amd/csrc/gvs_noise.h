@@ -322,19 +322,23 @@ GVS_SR_FN void nx_store(const NxArgs& a, uint32_t i, bool len_ok, uint32_t lane,
 
 // One handshake's phase: load, the schedule, store (live: not a tail quad's
 // repeat of the last item)
-template <int PH, class Q>
+// CHACHAPOLY: the suite's cipher, which only the protocol name of phase A sees
+template <int PH, bool CHACHAPOLY = false, class Q>
 GVS_SR_FN_NI void nx_item(Q& q, const NxArgs& a, uint32_t i, bool live) {
   const uint32_t len1 = a.msg1_lens[i];
   const bool len_ok = (len1 >= 64u) & (len1 <= 64u + kNxPayload1Max);
   const uint32_t l1 = len_ok ? len1 - 64u : 0u;
   q.each([&](uint32_t lane, NxLane& L) {
     // "Noise_IX_25519_AESGCM_SHA512" zero-padded to 64 bytes: h0, and ck = h0
-    constexpr uint64_t kName[8] = {0x4e6f6973655f4958ull, 0x5f32353531395f41ull, 0x455347434d5f5348ull,
-                                   0x4135313200000000ull, 0, 0, 0, 0};
+    constexpr uint64_t kNameGcm[8] = {0x4e6f6973655f4958ull, 0x5f32353531395f41ull, 0x455347434d5f5348ull,
+                                      0x4135313200000000ull, 0, 0, 0, 0};
+    // "Noise_IX_25519_ChaChaPoly_SHA512": 32 bytes, padded the same way
+    constexpr uint64_t kNameCp[8] = {0x4e6f6973655f4958ull, 0x5f32353531395f43ull, 0x6861436861506f6cull,
+                                     0x795f534841353132ull, 0, 0, 0, 0};
     const uint8_t* st = a.st + 128u * (uint64_t)i + (lane >= 2u ? 64u : 0u);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      L.key[j] = PH == kNxA ? kName[j] : ld_be64(st + 8 * j);
+      L.key[j] = PH == kNxA ? (CHACHAPOLY ? kNameCp[j] : kNameGcm[j]) : ld_be64(st + 8 * j);
       L.hs[j] = L.ps[j] = L.mb[j] = L.r[j] = 0;
     }
     L.act = L.last = 0;
@@ -371,6 +375,16 @@ __global__ void __launch_bounds__(kXThreads) k_noise_ix(NxArgs a) {
   NxQuadDev q;
   q.lane = threadIdx.x & 3u;
   nx_item<PH>(q, a, kk, k < a.n);
+}
+
+// Phase A of Noise_IX_25519_ChaChaPoly_SHA512: the same schedule from the
+// other protocol name.  Phases B and C do not see the name.
+__global__ void __launch_bounds__(kXThreads) k_noise_ix_a_chachapoly(NxArgs a) {
+  const uint32_t k = blockIdx.x * kXItems + (threadIdx.x >> 2);
+  const uint32_t kk = k < a.n ? k : a.n - 1;
+  NxQuadDev q;
+  q.lane = threadIdx.x & 3u;
+  nx_item<kNxA, true>(q, a, kk, k < a.n);
 }
 
 // What the chain's first launches read, put where their fixed strides want

@@ -7,15 +7,20 @@ DH of grapevine_amd.x25519, and the two halves of the IX pattern
 the tests compare the device call (`ObliviousStore.noise_ix_respond`,
 gvs_noise_ix_respond) against.  The AEAD is passed in: `seal(key, iv, aad,
 plaintext) -> ciphertext | tag` and `open_(key, iv, aad, ciphertext | tag) ->
-plaintext or None` (the tests pass tests/test_aead.py's).  Not constant time:
-for tests, tools and reference clients.
+plaintext or None` (the tests pass tests/test_aead.py's).  `cipher=
+abi.CIPHER_CHACHAPOLY` selects Noise_IX_25519_ChaChaPoly_SHA512 instead: the
+other protocol name, the little-endian nonce, and grapevine_amd.chachapoly for
+an AEAD that is not passed.  Not constant time: for tests, tools and reference
+clients.
 """
 import hashlib
 
-from . import abi
+from . import abi, chachapoly
 from .x25519 import noise_hkdf, x25519
 
 PROTOCOL_NAME = b"Noise_IX_25519_AESGCM_SHA512"
+PROTOCOL_NAMES = {abi.CIPHER_AESGCM: PROTOCOL_NAME, abi.CIPHER_CHACHAPOLY: b"Noise_IX_25519_ChaChaPoly_SHA512"}
+NONCES = {abi.CIPHER_AESGCM: abi.noise_iv, abi.CIPHER_CHACHAPOLY: abi.noise_nonce_chachapoly}
 DHLEN, HASHLEN, TAGLEN = 32, 64, 16
 
 
@@ -27,11 +32,14 @@ class SymmetricState:
     """§5.2, with the CipherState (§5.1) folded in: k is None until the first
     MixKey, and every MixKey sets the nonce back to 0."""
 
-    def __init__(self, seal, open_):
+    def __init__(self, seal, open_, cipher=abi.CIPHER_AESGCM):
         # InitializeSymmetric: a name of at most HASHLEN bytes is zero-padded
-        self.h = PROTOCOL_NAME.ljust(HASHLEN, b"\0") if len(PROTOCOL_NAME) <= HASHLEN else \
-            hashlib.sha512(PROTOCOL_NAME).digest()
+        name = PROTOCOL_NAMES[cipher]
+        self.h = name.ljust(HASHLEN, b"\0") if len(name) <= HASHLEN else hashlib.sha512(name).digest()
         self.ck, self.k, self.n = self.h, None, 0
+        self.nonce = NONCES[cipher]
+        if cipher == abi.CIPHER_CHACHAPOLY:
+            seal, open_ = seal or chachapoly.seal, open_ or chachapoly.open_
         self.seal, self.open_ = seal, open_
 
     def mix_hash(self, data):
@@ -45,7 +53,7 @@ class SymmetricState:
         if self.k is None:
             ct = bytes(plaintext)
         else:
-            ct = self.seal(self.k, abi.noise_iv(self.n), self.h, bytes(plaintext))
+            ct = self.seal(self.k, self.nonce(self.n), self.h, bytes(plaintext))
             self.n += 1
         self.mix_hash(ct)
         return ct
@@ -54,7 +62,7 @@ class SymmetricState:
         if self.k is None:
             pt = bytes(ct)
         else:
-            pt = self.open_(self.k, abi.noise_iv(self.n), self.h, bytes(ct))
+            pt = self.open_(self.k, self.nonce(self.n), self.h, bytes(ct))
             if pt is None:
                 raise HandshakeError("a handshake ciphertext does not verify")
             self.n += 1
@@ -80,9 +88,10 @@ class Initiator:
     -> (k1, k2, h); k1 seals what the initiator sends, k2 opens what it
     receives.  rs and payload2 hold what message 2 carried."""
 
-    def __init__(self, static_secret, ephemeral_secret, seal, open_, prologue=b""):
+    def __init__(self, static_secret, ephemeral_secret, seal=None, open_=None, prologue=b"",
+                 cipher=abi.CIPHER_AESGCM):
         self.s, self.e = bytes(static_secret), bytes(ephemeral_secret)
-        self.ss = SymmetricState(seal, open_)
+        self.ss = SymmetricState(seal, open_, cipher)
         self.ss.mix_hash(prologue)
         self.rs = self.payload2 = None
 
@@ -108,7 +117,7 @@ class Initiator:
         return k1, k2, ss.h
 
 
-def respond(static_secret, ephemeral_secret, msg1, payload, seal, prologue=b""):
+def respond(static_secret, ephemeral_secret, msg1, payload, seal=None, prologue=b"", cipher=abi.CIPHER_AESGCM):
     """The responder's half in one step: message 1 -> (message 2, k1, k2, h),
     or None where gvs_noise_ix_respond sets ok = 0 (a message 1 shorter than
     its two keys or longer than them and abi.NOISE_PAYLOAD1_MAX, a
@@ -116,7 +125,7 @@ def respond(static_secret, ephemeral_secret, msg1, payload, seal, prologue=b""):
     the responder sends."""
     if not 2 * DHLEN <= len(msg1) <= 2 * DHLEN + abi.NOISE_PAYLOAD1_MAX:
         return None
-    ss = SymmetricState(seal, None)
+    ss = SymmetricState(seal, None, cipher)
     ss.mix_hash(prologue)
     re = msg1[:DHLEN]
     ss.mix_hash(re)                                   # e

@@ -43,6 +43,9 @@ EXPORTED = (
     "gvs_x25519", "gvs_x25519_device", "gvs_noise_hkdf", "gvs_noise_hkdf_device",
     "gvs_noise_ix_respond", "gvs_noise_ix_respond_device",
     "gvs_noise_ix_respond_long", "gvs_noise_ix_respond_long_device",
+    "gvs_chachapoly_open", "gvs_chachapoly_open_device", "gvs_chachapoly_seal", "gvs_chachapoly_seal_device",
+    "gvs_process_wire_batch_channel_cipher", "gvs_process_wire_batch_channel_cipher_device",
+    "gvs_noise_ix_respond_cipher", "gvs_noise_ix_respond_cipher_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -91,12 +94,16 @@ def load_library(path=None):
     lib.gvs_process_wire_batch_channel.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32,
                                                    vp, vp, vp, vp]
     lib.gvs_process_wire_batch_channel_device.argtypes = lib.gvs_process_wire_batch_channel.argtypes
+    lib.gvs_process_wire_batch_channel_cipher.argtypes = lib.gvs_process_wire_batch_channel_cipher_device.argtypes = \
+        [vp, u32] + lib.gvs_process_wire_batch_channel.argtypes[1:]
     lib.gvs_aead_open.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, vp]
     lib.gvs_aead_open_device.argtypes = lib.gvs_aead_open.argtypes
     lib.gvs_aead_seal.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, u32, vp]
     lib.gvs_aead_seal_device.argtypes = lib.gvs_aead_seal.argtypes
     lib.gvs_aead_open_long.argtypes = lib.gvs_aead_open_long_device.argtypes = lib.gvs_aead_open.argtypes
     lib.gvs_aead_seal_long.argtypes = lib.gvs_aead_seal_long_device.argtypes = lib.gvs_aead_seal.argtypes
+    lib.gvs_chachapoly_open.argtypes = lib.gvs_chachapoly_open_device.argtypes = lib.gvs_aead_open.argtypes
+    lib.gvs_chachapoly_seal.argtypes = lib.gvs_chachapoly_seal_device.argtypes = lib.gvs_aead_seal.argtypes
     lib.gvs_challenge_derive.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_challenge_derive_device.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_sr25519_verify.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp]
@@ -113,6 +120,8 @@ def load_library(path=None):
     lib.gvs_noise_ix_respond_device.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
     lib.gvs_noise_ix_respond_long.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
     lib.gvs_noise_ix_respond_long_device.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
+    lib.gvs_noise_ix_respond_cipher.argtypes = lib.gvs_noise_ix_respond_cipher_device.argtypes = \
+        [vp, u32] + abi.NOISE_IX_RESPOND_ARGTYPES[1:]
     lib.gvs_wire_decode_device.argtypes =[vp, vp, u32, vp, u32, vp, vp, vp, vp]
     lib.gvs_wire_encode_device.argtypes = [vp, vp, u32, vp, u32, vp]
     lib.gvs_process_batches.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(u32)]
@@ -423,13 +432,16 @@ class ObliviousStore:
         return res
 
     def process_wire_batch_channel(self, msgs, times, seeds, draws, open_keys, open_ivs, seal_keys,
-                                   seal_ivs, in_stride=None, out_stride=None):
+                                   seal_ivs, in_stride=None, out_stride=None, cipher=None):
         """process_wire_batch_seeded behind the channel cipher
         (gvs_process_wire_batch_channel): msgs are the requests as ciphertext
         | tag under open_keys[k] (n, 32) / open_ivs[k] (n, 12, `abi.noise_iv`),
         and the responses come back as ciphertext | tag under seal_keys[k] /
         seal_ivs[k].  A request whose tag fails answers b"" with status
-        WIRE_BAD_CHANNEL_TAG.  -> what process_wire_batch_seeded returns."""
+        WIRE_BAD_CHANNEL_TAG.  cipher: abi.CIPHER_AESGCM or
+        abi.CIPHER_CHACHAPOLY (nonces from `abi.noise_nonce_chachapoly`)
+        through gvs_process_wire_batch_channel_cipher; None is the call
+        above.  -> what process_wire_batch_seeded returns."""
         if in_stride is None:
             in_stride = -(-max([len(m) for m in msgs] + [1]) // 16) * 16
         if out_stride is None:
@@ -445,15 +457,18 @@ class ObliviousStore:
         seeds, draws = self._seeds_draws(seeds, draws, n)
         keys = [np.ascontiguousarray(a, np.uint8).reshape(n, w)
                 for a, w in ((open_keys, 32), (open_ivs, 12), (seal_keys, 32), (seal_ivs, 12))]
-        self._check(self.lib.gvs_process_wire_batch_channel(
-            self.h, slab.ctypes.data, stride, lens.ctypes.data, n, times.ctypes.data,
+        fn, head = self.lib.gvs_process_wire_batch_channel, [self.h]
+        if cipher is not None:
+            fn, head = self.lib.gvs_process_wire_batch_channel_cipher, [self.h, cipher]
+        self._check(fn(
+            *head, slab.ctypes.data, stride, lens.ctypes.data, n, times.ctypes.data,
             seeds.ctypes.data if seeds is not None else None,
             draws.ctypes.data if draws is not None else None, *[a.ctypes.data for a in keys],
             out.ctypes.data, out_stride, out_lens.ctypes.data, sigs.ctypes.data, status.ctypes.data,
             chal.ctypes.data))
         return [out[k, :out_lens[k]].tobytes() for k in range(n)], sigs, status, chal
 
-    def _aead(self, seal, keys, ivs, msgs, aads, long=False):
+    def _aead(self, seal, keys, ivs, msgs, aads, long=False, name="gvs_aead"):
         n = len(msgs)
         keys = np.ascontiguousarray(keys, np.uint8).reshape(n, 32)
         ivs = np.ascontiguousarray(ivs, np.uint8).reshape(n, 12)
@@ -467,7 +482,7 @@ class ObliviousStore:
         out = np.zeros((n, out_stride), np.uint8)
         out_lens = np.zeros(n, np.uint32)
         ok = np.ones(n, np.uint32)
-        fn = getattr(self.lib, ("gvs_aead_seal" if seal else "gvs_aead_open") + ("_long" if long else ""))
+        fn = getattr(self.lib, name + ("_seal" if seal else "_open") + ("_long" if long else ""))
         self._check(fn(self.h, keys.ctypes.data, ivs.ctypes.data,
                        aad.ctypes.data if aad is not None else None, aad_stride,
                        aad_lens.ctypes.data if aad is not None else None, slab.ctypes.data, stride,
@@ -500,6 +515,18 @@ class ObliviousStore:
         """aead_open for whole Noise messages (gvs_aead_open_long): ciphertext
         | tag of up to 65 535 bytes -> (plaintexts, verdicts, output slab)."""
         out, out_lens, ok = self._aead(False, keys, ivs, msgs, aads, long=True)
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))], ok, out
+
+    def chachapoly_seal(self, keys, nonces, msgs, aads=None):
+        """aead_seal with ChaCha20-Poly1305 (gvs_chachapoly_seal): the same
+        arguments, nonces (n, 12) where it takes ivs."""
+        out, out_lens, _ = self._aead(True, keys, nonces, msgs, aads, name="gvs_chachapoly")
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))]
+
+    def chachapoly_open(self, keys, nonces, msgs, aads=None):
+        """aead_open with ChaCha20-Poly1305 (gvs_chachapoly_open) ->
+        (plaintexts, verdicts, output slab)."""
+        out, out_lens, ok = self._aead(False, keys, nonces, msgs, aads, name="gvs_chachapoly")
         return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))], ok, out
 
     def challenge_derive(self, seeds, draws):
@@ -584,16 +611,22 @@ class ObliviousStore:
         return out1, out2
 
     def noise_ix_respond(self, static_secret, ephemerals, msg1, payload=b"", prologue=b"",
-                         msg2_stride=None):
+                         msg2_stride=None, cipher=None):
         """The responder's side of n Noise_IX_25519_AESGCM_SHA512 handshakes
         on the device (gvs_noise_ix_respond): static_secret 32 bytes,
         ephemerals (n, 32) fresh secrets, msg1 a list of n first messages,
         payload one byte string for all or a list of n of one length, prologue
         bytes -> (list of n second messages, recv_keys (n, 32), send_keys
         (n, 32), hashes (n, 64), (n,) bool, the (n, stride) message-2 slab).  A
-        handshake that fails is b"" with zero keys and hash.  The form on
-        torch tensors is `noise_ix_respond_device`."""
-        return self._noise_ix_respond(self.lib.gvs_noise_ix_respond, 1, static_secret, ephemerals, msg1,
+        handshake that fails is b"" with zero keys and hash.  cipher:
+        abi.CIPHER_AESGCM or abi.CIPHER_CHACHAPOLY
+        (Noise_IX_25519_ChaChaPoly_SHA512) through gvs_noise_ix_respond_cipher;
+        None is the call above.  The form on torch tensors is
+        `noise_ix_respond_device`."""
+        fn = self.lib.gvs_noise_ix_respond
+        if cipher is not None:
+            fn = lambda h, *rest: self.lib.gvs_noise_ix_respond_cipher(h, cipher, *rest)
+        return self._noise_ix_respond(fn, 1, static_secret, ephemerals, msg1,
                                       payload, prologue, msg2_stride)
 
     def noise_ix_respond_long(self, static_secret, ephemerals, msg1, payload=b"", prologue=b"",
@@ -631,7 +664,8 @@ class ObliviousStore:
         return [msg2[k, :m2l[k]].tobytes() for k in range(n)], rk, sk, hh, ok.astype(bool), msg2
 
     def noise_ix_respond_device(self, static_secret, ephemerals, msg1, msg1_lens, payload, payload_len,
-                                msg2, msg2_lens, recv_keys, send_keys, hashes, ok, prologue=b"", long=False):
+                                msg2, msg2_lens, recv_keys, send_keys, hashes, ok, prologue=b"", long=False,
+                                cipher=None):
         """gvs_noise_ix_respond_device on torch CUDA tensors: ephemerals
         (n, >= 32 contiguous 32), msg1 (n, stride) uint8, msg1_lens (n,) int32,
         payload (n, stride) uint8, a 1-D tensor (one payload for all) or None,
@@ -639,13 +673,18 @@ class ObliviousStore:
         recv_keys / send_keys (n, 32), hashes (n, 64) or None, ok (n,) int32,
         all written in place.  The caller synchronises its own streams first.
         long: gvs_noise_ix_respond_long_device, whose payload and msg2 rows are
-        16-byte aligned, with strides that are multiples of 16."""
+        16-byte aligned, with strides that are multiples of 16.  cipher (not
+        with long): gvs_noise_ix_respond_cipher_device."""
         n = msg1.shape[0]
         ptr = lambda t: t.data_ptr() if t is not None else None
         pstride = 0 if payload is None or payload.dim() == 1 else payload.stride(0)
-        fn = self.lib.gvs_noise_ix_respond_long_device if long else self.lib.gvs_noise_ix_respond_device
+        fn, head = self.lib.gvs_noise_ix_respond_long_device if long else self.lib.gvs_noise_ix_respond_device, [self.h]
+        if cipher is not None:
+            if long:
+                raise ValueError("noise_ix_respond_device: the long form has no cipher choice")
+            fn, head = self.lib.gvs_noise_ix_respond_cipher_device, [self.h, cipher]
         self._check(fn(
-            self.h, bytes(static_secret), bytes(prologue), len(prologue), ptr(ephemerals), ptr(msg1),
+            *head, bytes(static_secret), bytes(prologue), len(prologue), ptr(ephemerals), ptr(msg1),
             msg1.stride(0), ptr(msg1_lens), ptr(payload), pstride, payload_len, n, ptr(msg2), msg2.stride(0),
             ptr(msg2_lens), ptr(recv_keys), ptr(send_keys), ptr(hashes), ptr(ok)))
 

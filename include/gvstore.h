@@ -373,6 +373,35 @@ int gvs_process_wire_batch_channel_device(gvs_handle *h, const void *d_in, uint3
                                           const void *d_seal_ivs, void *d_out, uint32_t out_stride,
                                           uint32_t *d_out_lens, void *d_sigs,
                                           uint32_t *d_decode_status, void *d_challenges_out);
+/* The channel calls with the cipher chosen: Noise names two, and a channel
+ * uses one of them for its handshake and its transport.  GVS_CIPHER_AESGCM
+ * launches exactly what gvs_process_wire_batch_channel launches (which is this
+ * call with that value) and returns its bytes; GVS_CIPHER_CHACHAPOLY opens and
+ * seals with gvs_chachapoly_open / gvs_chachapoly_seal instead, the nonces in
+ * open_ivs / seal_ivs then 0^32 | le64(counter); any other value is
+ * GVS_ERR_INVALID_ARG.  Everything else is as above, failures included.
+ * [D: the snapshot of the reference names its crates, not its suite string;
+ * AESGCM stays the default, and offering ChaChaPoly beside it is this
+ * project's decision, for integrators who control both ends.] */
+#define GVS_CIPHER_AESGCM 0u
+#define GVS_CIPHER_CHACHAPOLY 1u
+int gvs_process_wire_batch_channel_cipher(gvs_handle *h, uint32_t cipher, const uint8_t *in,
+                                          uint32_t in_stride, const uint32_t *in_lens, uint32_t n,
+                                          const uint64_t *times, const uint8_t *seeds,
+                                          const uint64_t *draws, const uint8_t *open_keys,
+                                          const uint8_t *open_ivs, const uint8_t *seal_keys,
+                                          const uint8_t *seal_ivs, uint8_t *out, uint32_t out_stride,
+                                          uint32_t *out_lens, uint8_t *sigs, uint32_t *decode_status,
+                                          uint8_t *challenges_out);
+int gvs_process_wire_batch_channel_cipher_device(gvs_handle *h, uint32_t cipher, const void *d_in,
+                                                 uint32_t in_stride, const uint32_t *d_in_lens,
+                                                 uint32_t n, const uint64_t *d_times,
+                                                 const void *d_seeds, const uint64_t *d_draws,
+                                                 const void *d_open_keys, const void *d_open_ivs,
+                                                 const void *d_seal_keys, const void *d_seal_ivs,
+                                                 void *d_out, uint32_t out_stride,
+                                                 uint32_t *d_out_lens, void *d_sigs,
+                                                 uint32_t *d_decode_status, void *d_challenges_out);
 
 /* AES-256-GCM (NIST SP 800-38D, 96-bit IV, 128-bit tag), batched, every
  * message under a key and an IV of its own: keys n x 32 B and ivs n x 12 B
@@ -414,6 +443,32 @@ int gvs_aead_seal_device(gvs_handle *h, const void *d_keys, const void *d_ivs, c
                          uint32_t aad_stride, const uint32_t *d_aad_lens, const void *d_in,
                          uint32_t in_stride, const uint32_t *d_in_lens, uint32_t n, void *d_out,
                          uint32_t out_stride, uint32_t *d_out_lens);
+
+/* ChaCha20-Poly1305 (RFC 8439 §2.8: 96-bit nonce, 32-bit block counter,
+ * 128-bit tag), Noise's ChaChaPoly, batched the same way:
+ * the argument lists, limits, alignment rules and per-message failures of
+ * gvs_aead_open / gvs_aead_seal, word for word, with `nonces` (n x 12 B, for
+ * Noise 0^32 | le64(counter)) where they take ivs.  One row of 16 lanes per
+ * message; no table, and no address that follows a key or the text.  Stage
+ * marks chachapoly_open and chachapoly_seal.  Texts up to GVS_AEAD_TEXT_MAX
+ * only: this cipher has no long form. */
+int gvs_chachapoly_open(gvs_handle *h, const uint8_t *keys, const uint8_t *nonces,
+                        const uint8_t *aad, uint32_t aad_stride, const uint32_t *aad_lens,
+                        const uint8_t *in, uint32_t in_stride, const uint32_t *in_lens, uint32_t n,
+                        uint8_t *out, uint32_t out_stride, uint32_t *out_lens, uint32_t *ok);
+int gvs_chachapoly_open_device(gvs_handle *h, const void *d_keys, const void *d_nonces,
+                               const void *d_aad, uint32_t aad_stride, const uint32_t *d_aad_lens,
+                               const void *d_in, uint32_t in_stride, const uint32_t *d_in_lens,
+                               uint32_t n, void *d_out, uint32_t out_stride, uint32_t *d_out_lens,
+                               uint32_t *d_ok);
+int gvs_chachapoly_seal(gvs_handle *h, const uint8_t *keys, const uint8_t *nonces,
+                        const uint8_t *aad, uint32_t aad_stride, const uint32_t *aad_lens,
+                        const uint8_t *in, uint32_t in_stride, const uint32_t *in_lens, uint32_t n,
+                        uint8_t *out, uint32_t out_stride, uint32_t *out_lens);
+int gvs_chachapoly_seal_device(gvs_handle *h, const void *d_keys, const void *d_nonces,
+                               const void *d_aad, uint32_t aad_stride, const uint32_t *d_aad_lens,
+                               const void *d_in, uint32_t in_stride, const uint32_t *d_in_lens,
+                               uint32_t n, void *d_out, uint32_t out_stride, uint32_t *d_out_lens);
 
 /* The long form of the same cipher, for whole Noise messages (ciphertext + tag
  * <= 65 535 bytes): the argument lists, the outputs and the per-message
@@ -571,6 +626,31 @@ int gvs_noise_ix_respond_device(gvs_handle *h, const uint8_t static_secret[32],
                                 void *d_msg2, uint32_t msg2_stride, uint32_t *d_msg2_lens,
                                 void *d_recv_keys, void *d_send_keys, void *d_hashes,
                                 uint32_t *d_ok);
+/* The same responder with the suite chosen.  GVS_CIPHER_AESGCM is
+ * gvs_noise_ix_respond, launch for launch and byte for byte;
+ * GVS_CIPHER_CHACHAPOLY is Noise_IX_25519_ChaChaPoly_SHA512: the other
+ * protocol name under h0 = ck and gvs_chachapoly_seal for both of message 2's
+ * ciphertexts, everything else the same chain, and keys that go to the
+ * channel call with the same cipher.  Any other value is
+ * GVS_ERR_INVALID_ARG.  The long forms below are AESGCM only: a long
+ * ChaChaPoly kernel is out of scope. */
+int gvs_noise_ix_respond_cipher(gvs_handle *h, uint32_t cipher, const uint8_t static_secret[32],
+                                const uint8_t *prologue, uint32_t prologue_len,
+                                const uint8_t *ephemerals, const uint8_t *msg1,
+                                uint32_t msg1_stride, const uint32_t *msg1_lens,
+                                const uint8_t *payload, uint32_t payload_stride,
+                                uint32_t payload_len, uint32_t n, uint8_t *msg2,
+                                uint32_t msg2_stride, uint32_t *msg2_lens, uint8_t *recv_keys,
+                                uint8_t *send_keys, uint8_t *hashes, uint32_t *ok);
+int gvs_noise_ix_respond_cipher_device(gvs_handle *h, uint32_t cipher,
+                                       const uint8_t static_secret[32], const uint8_t *prologue,
+                                       uint32_t prologue_len, const void *d_ephemerals,
+                                       const void *d_msg1, uint32_t msg1_stride,
+                                       const uint32_t *d_msg1_lens, const void *d_payload,
+                                       uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                                       void *d_msg2, uint32_t msg2_stride, uint32_t *d_msg2_lens,
+                                       void *d_recv_keys, void *d_send_keys, void *d_hashes,
+                                       uint32_t *d_ok);
 
 /* The same handshake with a message-2 payload of up to
  * GVS_NOISE_PAYLOAD2_LONG_MAX bytes (message 2 = 96 + payload_len <= 65 535,
