@@ -20,8 +20,9 @@ XHOST := tests/libxhost.so
 NHOST := tests/libnhost.so
 NLONGHOST := tests/libnlonghost.so
 CPHOST := tests/libchachapolyhost.so
+CPLONGHOST := tests/libchachapolylonghost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) $(CPLONGHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -75,11 +76,16 @@ $(NLONGHOST): tests/noise_long_host.cpp tests/noise_host.cpp tests/aead_host.cpp
 $(CPHOST): tests/chachapoly_host.cpp grapevine_amd/csrc/gvs_chachapoly.h grapevine_amd/csrc/gvs_chacha_rounds.h grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/chachapoly_host.cpp
 
+# the long ChaCha20-Poly1305 schedule (256 thread states stepped through the
+# phases of k_chachapoly_long) built for the CPU (tests/test_chachapoly_long.py)
+$(CPLONGHOST): tests/chachapoly_long_host.cpp grapevine_amd/csrc/gvs_chachapoly_long.h grapevine_amd/csrc/gvs_chachapoly.h grapevine_amd/csrc/gvs_chacha_rounds.h grapevine_amd/csrc/gvs_aead_long.h grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/chachapoly_long_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) $(CPLONGHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

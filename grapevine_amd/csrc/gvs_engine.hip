@@ -39,6 +39,7 @@
 #include "gvs_aead.h"
 #include "gvs_aead_long.h"
 #include "gvs_chachapoly.h"
+#include "gvs_chachapoly_long.h"
 #include "gvs_noise_long.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
@@ -2586,6 +2587,15 @@ static void enqueue_aead_long(gvs_handle* h, bool seal, AeadArgs a) {
     hipLaunchKernelGGL(k_aead_long<false>, dim3(a.n), dim3(kAlThreads), 0, h->stream, a);
 }
 
+// ChaCha20-Poly1305's long form (gvs_chachapoly_long.h): one workgroup per message, no table
+static void enqueue_chachapoly_long(gvs_handle* h, bool seal, AeadArgs a) {
+  if (!a.n) return;
+  if (seal)
+    hipLaunchKernelGGL(k_chachapoly_long<true>, dim3(a.n), dim3(kClThreads), 0, h->stream, a);
+  else
+    hipLaunchKernelGGL(k_chachapoly_long<false>, dim3(a.n), dim3(kClThreads), 0, h->stream, a);
+}
+
 // decode -> (challenge check) -> the batch -> encode, all on the engine
 // stream; the request and response slabs live in the handle's host-API
 // staging.
@@ -3170,12 +3180,12 @@ struct NoiseIxCall {
   uint32_t* msg2_lens;
   uint8_t *recv, *send, *hashes;
   uint32_t* ok;
-  bool lng = false;  // the long calls: k_aead_long and k_noise_ix_tail (gvs_noise_long.h), with their limits
-  uint32_t cipher = GVS_CIPHER_AESGCM;  // GVS_CIPHER_CHACHAPOLY: the other suite (short calls only)
+  bool lng = false;  // the long calls: a long second seal and k_noise_ix_tail (gvs_noise_long.h), with their limits
+  uint32_t cipher = GVS_CIPHER_AESGCM;  // GVS_CIPHER_CHACHAPOLY: the other suite
 };
 
 static bool noise_ix_call_ok(gvs_handle* h, const NoiseIxCall& c) {
-  return h && c.cipher <= GVS_CIPHER_CHACHAPOLY && !(c.lng && c.cipher != GVS_CIPHER_AESGCM) && c.static_secret &&
+  return h && c.cipher <= GVS_CIPHER_CHACHAPOLY && c.static_secret &&
          c.prologue_len <= sr::kNxPrologueMax && (!c.prologue_len || c.prologue) &&
          c.payload_len <= (c.lng ? sr::kNxPayload2LongMax : kAeadTextMax) && (!c.payload_len || c.payload) &&
          (!c.payload_stride || c.payload_stride >= c.payload_len) && c.msg1_stride >= 64 &&
@@ -3185,7 +3195,7 @@ static bool noise_ix_call_ok(gvs_handle* h, const NoiseIxCall& c) {
 }
 
 // The second seal's text stride: payload 2 in whole 16-byte blocks.  The long
-// chain hands k_aead_long the caller's own rows (0: no text rows in the work
+// chain hands its long seal the caller's own rows (0: no text rows in the work
 // area); only one payload for all is spread into rows, because the kernel
 // refuses a message longer than its in_stride and so cannot read it in place.
 static uint32_t noise_ix_text2(const NoiseIxCall& c) {
@@ -3207,8 +3217,8 @@ static size_t noise_ix_work_bytes(const NoiseIxCall& c) {
 
 // The chain on the handle's stream, synchronous: the gather, one k_x25519 over
 // 4n + 1 items, then k_noise_ix<A>, k_aead<true>, k_noise_ix<B>, k_aead<true>,
-// k_noise_ix<C>; the long chain ends with k_aead_long<true> and
-// k_noise_ix_tail instead.  c's arrays are device memory; `work` holds
+// k_noise_ix<C>; the long chain ends with k_aead_long<true> (ChaChaPoly:
+// k_chachapoly_long<true>) and k_noise_ix_tail instead.  c's arrays are device memory; `work` holds
 // noise_ix_work_bytes, 16-byte aligned.
 static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   const bool cp = c.cipher == GVS_CIPHER_CHACHAPOLY;
@@ -3285,8 +3295,13 @@ static int noise_ix_run(gvs_handle* h, const NoiseIxCall& c, uint8_t* work) {
   hipLaunchKernelGGL(sr::k_noise_ix<sr::kNxB>, grid, block, 0, h->stream, a);
   mark(h, "noise_b");
   if (c.lng) {
-    enqueue_aead_long(h, true, s2);
-    mark(h, "aead_seal_long");
+    if (cp) {
+      enqueue_chachapoly_long(h, true, s2);
+      mark(h, "chachapoly_seal_long");
+    } else {
+      enqueue_aead_long(h, true, s2);
+      mark(h, "aead_seal_long");
+    }
     hipLaunchKernelGGL(sr::k_noise_ix_tail, dim3((n + sr::kSrThreads - 1) / sr::kSrThreads), dim3(sr::kSrThreads), 0,
                        h->stream, a);
     mark(h, "noise_tail");
@@ -3429,6 +3444,34 @@ int gvs_noise_ix_respond_long(gvs_handle* h, const uint8_t static_secret[32], co
                                       recv_keys, send_keys, hashes, ok, true});
 }
 
+// the long responder with the suite chosen: GVS_CIPHER_AESGCM is the call
+// above; GVS_CIPHER_CHACHAPOLY takes phase A's other name, k_chachapoly<true>
+// for the first seal and k_chachapoly_long<true> for the second
+int gvs_noise_ix_respond_long_cipher_device(gvs_handle* h, uint32_t cipher, const uint8_t static_secret[32],
+                                            const uint8_t* prologue, uint32_t prologue_len,
+                                            const void* d_ephemerals, const void* d_msg1, uint32_t msg1_stride,
+                                            const uint32_t* d_msg1_lens, const void* d_payload,
+                                            uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                                            void* d_msg2, uint32_t msg2_stride, uint32_t* d_msg2_lens,
+                                            void* d_recv_keys, void* d_send_keys, void* d_hashes, uint32_t* d_ok) {
+  return noise_ix_device(h, NoiseIxCall{static_secret, prologue, prologue_len, (const uint8_t*)d_ephemerals,
+                                        (const uint8_t*)d_msg1, msg1_stride, d_msg1_lens, (const uint8_t*)d_payload,
+                                        payload_stride, payload_len, n, (uint8_t*)d_msg2, msg2_stride, d_msg2_lens,
+                                        (uint8_t*)d_recv_keys, (uint8_t*)d_send_keys, (uint8_t*)d_hashes, d_ok,
+                                        true, cipher});
+}
+
+int gvs_noise_ix_respond_long_cipher(gvs_handle* h, uint32_t cipher, const uint8_t static_secret[32],
+                                     const uint8_t* prologue, uint32_t prologue_len, const uint8_t* ephemerals,
+                                     const uint8_t* msg1, uint32_t msg1_stride, const uint32_t* msg1_lens,
+                                     const uint8_t* payload, uint32_t payload_stride, uint32_t payload_len,
+                                     uint32_t n, uint8_t* msg2, uint32_t msg2_stride, uint32_t* msg2_lens,
+                                     uint8_t* recv_keys, uint8_t* send_keys, uint8_t* hashes, uint32_t* ok) {
+  return noise_ix_host(h, NoiseIxCall{static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride, msg1_lens,
+                                      payload, payload_stride, payload_len, n, msg2, msg2_stride, msg2_lens,
+                                      recv_keys, send_keys, hashes, ok, true, cipher});
+}
+
 // ---------------------------------------------------- channel cipher alone
 
 struct AeadCall {
@@ -3479,6 +3522,9 @@ static int aead_device(gvs_handle* h, const AeadCall& c, bool seal, bool lng, ui
   a.out_stride = c.out_stride;
   a.out_lens = c.out_lens;
   a.ok = c.ok;
+  if (lng && cipher == GVS_CIPHER_CHACHAPOLY)
+    return launch_sync(h, seal ? "chachapoly_seal_long" : "chachapoly_open_long",
+                       [&] { enqueue_chachapoly_long(h, seal, a); });
   if (lng) return launch_sync(h, seal ? "aead_seal_long" : "aead_open_long", [&] { enqueue_aead_long(h, seal, a); });
   if (cipher == GVS_CIPHER_CHACHAPOLY)
     return launch_sync(h, seal ? "chachapoly_seal" : "chachapoly_open", [&] { enqueue_chachapoly(h, seal, a); });
@@ -3624,6 +3670,39 @@ int gvs_aead_seal_long(gvs_handle* h, const uint8_t* keys, const uint8_t* ivs, c
                        uint32_t* out_lens) {
   return aead_host(h, AeadCall{keys, ivs, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
                                out_stride, out_lens, nullptr}, true, true);
+}
+
+// ChaCha20-Poly1305's long forms (gvs_chachapoly_long.h): the same argument lists and limits
+int gvs_chachapoly_open_long_device(gvs_handle* h, const void* d_keys, const void* d_nonces, const void* d_aad,
+                                    uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                                    uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                                    uint32_t out_stride, uint32_t* d_out_lens, uint32_t* d_ok) {
+  return aead_device(h, AeadCall{d_keys, d_nonces, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, d_ok}, false, true, GVS_CIPHER_CHACHAPOLY);
+}
+
+int gvs_chachapoly_seal_long_device(gvs_handle* h, const void* d_keys, const void* d_nonces, const void* d_aad,
+                                    uint32_t aad_stride, const uint32_t* d_aad_lens, const void* d_in,
+                                    uint32_t in_stride, const uint32_t* d_in_lens, uint32_t n, void* d_out,
+                                    uint32_t out_stride, uint32_t* d_out_lens) {
+  return aead_device(h, AeadCall{d_keys, d_nonces, d_aad, aad_stride, d_aad_lens, d_in, in_stride, d_in_lens, n,
+                                 d_out, out_stride, d_out_lens, nullptr}, true, true, GVS_CIPHER_CHACHAPOLY);
+}
+
+int gvs_chachapoly_open_long(gvs_handle* h, const uint8_t* keys, const uint8_t* nonces, const uint8_t* aad,
+                             uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                             const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                             uint32_t* out_lens, uint32_t* ok) {
+  return aead_host(h, AeadCall{keys, nonces, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, ok}, false, true, GVS_CIPHER_CHACHAPOLY);
+}
+
+int gvs_chachapoly_seal_long(gvs_handle* h, const uint8_t* keys, const uint8_t* nonces, const uint8_t* aad,
+                             uint32_t aad_stride, const uint32_t* aad_lens, const uint8_t* in, uint32_t in_stride,
+                             const uint32_t* in_lens, uint32_t n, uint8_t* out, uint32_t out_stride,
+                             uint32_t* out_lens) {
+  return aead_host(h, AeadCall{keys, nonces, aad, aad_stride, aad_lens, in, in_stride, in_lens, n, out,
+                               out_stride, out_lens, nullptr}, true, true, GVS_CIPHER_CHACHAPOLY);
 }
 
 int gvs_set_expiry_cutoff(gvs_handle* h, uint64_t cutoff) {

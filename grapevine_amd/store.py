@@ -46,6 +46,9 @@ EXPORTED = (
     "gvs_chachapoly_open", "gvs_chachapoly_open_device", "gvs_chachapoly_seal", "gvs_chachapoly_seal_device",
     "gvs_process_wire_batch_channel_cipher", "gvs_process_wire_batch_channel_cipher_device",
     "gvs_noise_ix_respond_cipher", "gvs_noise_ix_respond_cipher_device",
+    "gvs_chachapoly_open_long", "gvs_chachapoly_open_long_device",
+    "gvs_chachapoly_seal_long", "gvs_chachapoly_seal_long_device",
+    "gvs_noise_ix_respond_long_cipher", "gvs_noise_ix_respond_long_cipher_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -104,6 +107,8 @@ def load_library(path=None):
     lib.gvs_aead_seal_long.argtypes = lib.gvs_aead_seal_long_device.argtypes = lib.gvs_aead_seal.argtypes
     lib.gvs_chachapoly_open.argtypes = lib.gvs_chachapoly_open_device.argtypes = lib.gvs_aead_open.argtypes
     lib.gvs_chachapoly_seal.argtypes = lib.gvs_chachapoly_seal_device.argtypes = lib.gvs_aead_seal.argtypes
+    lib.gvs_chachapoly_open_long.argtypes = lib.gvs_chachapoly_open_long_device.argtypes = lib.gvs_aead_open.argtypes
+    lib.gvs_chachapoly_seal_long.argtypes = lib.gvs_chachapoly_seal_long_device.argtypes = lib.gvs_aead_seal.argtypes
     lib.gvs_challenge_derive.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_challenge_derive_device.argtypes = [vp, vp, vp, u32, vp]
     lib.gvs_sr25519_verify.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp]
@@ -122,6 +127,8 @@ def load_library(path=None):
     lib.gvs_noise_ix_respond_long_device.argtypes = abi.NOISE_IX_RESPOND_ARGTYPES
     lib.gvs_noise_ix_respond_cipher.argtypes = lib.gvs_noise_ix_respond_cipher_device.argtypes = \
         [vp, u32] + abi.NOISE_IX_RESPOND_ARGTYPES[1:]
+    lib.gvs_noise_ix_respond_long_cipher.argtypes = lib.gvs_noise_ix_respond_long_cipher_device.argtypes = \
+        lib.gvs_noise_ix_respond_cipher.argtypes
     lib.gvs_wire_decode_device.argtypes =[vp, vp, u32, vp, u32, vp, vp, vp, vp]
     lib.gvs_wire_encode_device.argtypes = [vp, vp, u32, vp, u32, vp]
     lib.gvs_process_batches.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(u32)]
@@ -529,6 +536,18 @@ class ObliviousStore:
         out, out_lens, ok = self._aead(False, keys, nonces, msgs, aads, name="gvs_chachapoly")
         return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))], ok, out
 
+    def chachapoly_seal_long(self, keys, nonces, msgs, aads=None):
+        """chachapoly_seal for whole Noise messages (gvs_chachapoly_seal_long):
+        plaintexts of up to abi.AEAD_LONG_TEXT_MAX bytes, one workgroup per message."""
+        out, out_lens, _ = self._aead(True, keys, nonces, msgs, aads, long=True, name="gvs_chachapoly")
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))]
+
+    def chachapoly_open_long(self, keys, nonces, msgs, aads=None):
+        """chachapoly_open for whole Noise messages (gvs_chachapoly_open_long):
+        ciphertext | tag of up to 65 535 bytes -> (plaintexts, verdicts, output slab)."""
+        out, out_lens, ok = self._aead(False, keys, nonces, msgs, aads, long=True, name="gvs_chachapoly")
+        return [out[k, :out_lens[k]].tobytes() for k in range(len(msgs))], ok, out
+
     def challenge_derive(self, seeds, draws):
         """The challenge stream on the device (gvs_challenge_derive): seeds
         (n, 32) uint8, draws (n,) uint64 -> (n, 32) uint8, row k = draw number
@@ -630,14 +649,17 @@ class ObliviousStore:
                                       payload, prologue, msg2_stride)
 
     def noise_ix_respond_long(self, static_secret, ephemerals, msg1, payload=b"", prologue=b"",
-                              msg2_stride=None):
+                              msg2_stride=None, cipher=None):
         """noise_ix_respond with a payload of up to abi.NOISE_PAYLOAD2_LONG_MAX
         bytes inside message 2 (gvs_noise_ix_respond_long): the same arguments
         and results; msg2_stride is a multiple of 16 (default: 96 + the
-        payload's length, rounded up).  The form on torch tensors is
-        `noise_ix_respond_long_device`."""
-        return self._noise_ix_respond(self.lib.gvs_noise_ix_respond_long, 16, static_secret, ephemerals, msg1,
-                                      payload, prologue, msg2_stride)
+        payload's length, rounded up).  cipher: as in noise_ix_respond, through
+        gvs_noise_ix_respond_long_cipher; None is the call above.  The form on
+        torch tensors is `noise_ix_respond_long_device`."""
+        fn = self.lib.gvs_noise_ix_respond_long
+        if cipher is not None:
+            fn = lambda h, *rest: self.lib.gvs_noise_ix_respond_long_cipher(h, cipher, *rest)
+        return self._noise_ix_respond(fn, 16, static_secret, ephemerals, msg1, payload, prologue, msg2_stride)
 
     def _noise_ix_respond(self, fn, align, static_secret, ephemerals, msg1, payload, prologue, msg2_stride):
         """The host forms: payload rows and the default message-2 stride are
@@ -673,16 +695,16 @@ class ObliviousStore:
         recv_keys / send_keys (n, 32), hashes (n, 64) or None, ok (n,) int32,
         all written in place.  The caller synchronises its own streams first.
         long: gvs_noise_ix_respond_long_device, whose payload and msg2 rows are
-        16-byte aligned, with strides that are multiples of 16.  cipher (not
-        with long): gvs_noise_ix_respond_cipher_device."""
+        16-byte aligned, with strides that are multiples of 16.  cipher:
+        gvs_noise_ix_respond_cipher_device, or with long
+        gvs_noise_ix_respond_long_cipher_device."""
         n = msg1.shape[0]
         ptr = lambda t: t.data_ptr() if t is not None else None
         pstride = 0 if payload is None or payload.dim() == 1 else payload.stride(0)
         fn, head = self.lib.gvs_noise_ix_respond_long_device if long else self.lib.gvs_noise_ix_respond_device, [self.h]
         if cipher is not None:
-            if long:
-                raise ValueError("noise_ix_respond_device: the long form has no cipher choice")
-            fn, head = self.lib.gvs_noise_ix_respond_cipher_device, [self.h, cipher]
+            fn = self.lib.gvs_noise_ix_respond_long_cipher_device if long else self.lib.gvs_noise_ix_respond_cipher_device
+            head = [self.h, cipher]
         self._check(fn(
             *head, bytes(static_secret), bytes(prologue), len(prologue), ptr(ephemerals), ptr(msg1),
             msg1.stride(0), ptr(msg1_lens), ptr(payload), pstride, payload_len, n, ptr(msg2), msg2.stride(0),

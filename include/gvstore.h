@@ -450,8 +450,8 @@ int gvs_aead_seal_device(gvs_handle *h, const void *d_keys, const void *d_ivs, c
  * gvs_aead_open / gvs_aead_seal, word for word, with `nonces` (n x 12 B, for
  * Noise 0^32 | le64(counter)) where they take ivs.  One row of 16 lanes per
  * message; no table, and no address that follows a key or the text.  Stage
- * marks chachapoly_open and chachapoly_seal.  Texts up to GVS_AEAD_TEXT_MAX
- * only: this cipher has no long form. */
+ * marks chachapoly_open and chachapoly_seal.  Texts up to GVS_AEAD_TEXT_MAX;
+ * gvs_chachapoly_open_long / gvs_chachapoly_seal_long below take longer ones. */
 int gvs_chachapoly_open(gvs_handle *h, const uint8_t *keys, const uint8_t *nonces,
                         const uint8_t *aad, uint32_t aad_stride, const uint32_t *aad_lens,
                         const uint8_t *in, uint32_t in_stride, const uint32_t *in_lens, uint32_t n,
@@ -498,6 +498,33 @@ int gvs_aead_seal_long_device(gvs_handle *h, const void *d_keys, const void *d_i
                               uint32_t aad_stride, const uint32_t *d_aad_lens, const void *d_in,
                               uint32_t in_stride, const uint32_t *d_in_lens, uint32_t n, void *d_out,
                               uint32_t out_stride, uint32_t *d_out_lens);
+
+/* The long form of ChaCha20-Poly1305: the argument lists,
+ * limits (texts to GVS_AEAD_LONG_TEXT_MAX, strides multiples of 16 up to
+ * 65 536), staging cap (GVS_AEAD_LONG_STAGE_MAX) and per-message failures of
+ * gvs_aead_open_long / gvs_aead_seal_long, with `nonces` where they take ivs.
+ * One 256-thread workgroup per message, no table; texts of 0 ..
+ * GVS_AEAD_TEXT_MAX bytes are valid and give the bytes of the short calls.
+ * Stage marks chachapoly_open_long and chachapoly_seal_long. */
+int gvs_chachapoly_open_long(gvs_handle *h, const uint8_t *keys, const uint8_t *nonces,
+                             const uint8_t *aad, uint32_t aad_stride, const uint32_t *aad_lens,
+                             const uint8_t *in, uint32_t in_stride, const uint32_t *in_lens,
+                             uint32_t n, uint8_t *out, uint32_t out_stride, uint32_t *out_lens,
+                             uint32_t *ok);
+int gvs_chachapoly_open_long_device(gvs_handle *h, const void *d_keys, const void *d_nonces,
+                                    const void *d_aad, uint32_t aad_stride,
+                                    const uint32_t *d_aad_lens, const void *d_in, uint32_t in_stride,
+                                    const uint32_t *d_in_lens, uint32_t n, void *d_out,
+                                    uint32_t out_stride, uint32_t *d_out_lens, uint32_t *d_ok);
+int gvs_chachapoly_seal_long(gvs_handle *h, const uint8_t *keys, const uint8_t *nonces,
+                             const uint8_t *aad, uint32_t aad_stride, const uint32_t *aad_lens,
+                             const uint8_t *in, uint32_t in_stride, const uint32_t *in_lens,
+                             uint32_t n, uint8_t *out, uint32_t out_stride, uint32_t *out_lens);
+int gvs_chachapoly_seal_long_device(gvs_handle *h, const void *d_keys, const void *d_nonces,
+                                    const void *d_aad, uint32_t aad_stride,
+                                    const uint32_t *d_aad_lens, const void *d_in, uint32_t in_stride,
+                                    const uint32_t *d_in_lens, uint32_t n, void *d_out,
+                                    uint32_t out_stride, uint32_t *d_out_lens);
 
 /* The challenge stream alone: out[k] (32 B) = draw number draws[k] of
  * ChaCha20Rng(seeds[k]), that is bytes [32*(d&1), 32*(d&1)+32) of ChaCha20
@@ -632,8 +659,8 @@ int gvs_noise_ix_respond_device(gvs_handle *h, const uint8_t static_secret[32],
  * protocol name under h0 = ck and gvs_chachapoly_seal for both of message 2's
  * ciphertexts, everything else the same chain, and keys that go to the
  * channel call with the same cipher.  Any other value is
- * GVS_ERR_INVALID_ARG.  The long forms below are AESGCM only: a long
- * ChaChaPoly kernel is out of scope. */
+ * GVS_ERR_INVALID_ARG.  gvs_noise_ix_respond_long below is AESGCM;
+ * gvs_noise_ix_respond_long_cipher chooses the suite of the long form. */
 int gvs_noise_ix_respond_cipher(gvs_handle *h, uint32_t cipher, const uint8_t static_secret[32],
                                 const uint8_t *prologue, uint32_t prologue_len,
                                 const uint8_t *ephemerals, const uint8_t *msg1,
@@ -685,6 +712,31 @@ int gvs_noise_ix_respond_long_device(gvs_handle *h, const uint8_t static_secret[
                                      uint32_t msg2_stride, uint32_t *d_msg2_lens,
                                      void *d_recv_keys, void *d_send_keys, void *d_hashes,
                                      uint32_t *d_ok);
+
+/* The long responder with the suite chosen.  GVS_CIPHER_AESGCM is
+ * gvs_noise_ix_respond_long, launch for launch and byte for byte;
+ * GVS_CIPHER_CHACHAPOLY is Noise_IX_25519_ChaChaPoly_SHA512 with the same
+ * limits: gvs_chachapoly_seal for the first ciphertext of message 2 and the
+ * long ChaCha20-Poly1305 kernel for the payload's.  Any other value is
+ * GVS_ERR_INVALID_ARG. */
+int gvs_noise_ix_respond_long_cipher(gvs_handle *h, uint32_t cipher,
+                                     const uint8_t static_secret[32], const uint8_t *prologue,
+                                     uint32_t prologue_len, const uint8_t *ephemerals,
+                                     const uint8_t *msg1, uint32_t msg1_stride,
+                                     const uint32_t *msg1_lens, const uint8_t *payload,
+                                     uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                                     uint8_t *msg2, uint32_t msg2_stride, uint32_t *msg2_lens,
+                                     uint8_t *recv_keys, uint8_t *send_keys, uint8_t *hashes,
+                                     uint32_t *ok);
+int gvs_noise_ix_respond_long_cipher_device(gvs_handle *h, uint32_t cipher,
+                                            const uint8_t static_secret[32], const uint8_t *prologue,
+                                            uint32_t prologue_len, const void *d_ephemerals,
+                                            const void *d_msg1, uint32_t msg1_stride,
+                                            const uint32_t *d_msg1_lens, const void *d_payload,
+                                            uint32_t payload_stride, uint32_t payload_len,
+                                            uint32_t n, void *d_msg2, uint32_t msg2_stride,
+                                            uint32_t *d_msg2_lens, void *d_recv_keys,
+                                            void *d_send_keys, void *d_hashes, uint32_t *d_ok);
 
 /* Message expiry (README.md:86-99: the untrusted host supplies the time and
  * the expiry period).  From the next batch on, messages whose timestamp is
