@@ -21,8 +21,9 @@ NHOST := tests/libnhost.so
 NLONGHOST := tests/libnlonghost.so
 CPHOST := tests/libchachapolyhost.so
 CPLONGHOST := tests/libchachapolylonghost.so
+NINITHOST := tests/libninithost.so
 
-all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) $(CPLONGHOST) oracle
+all: $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) $(CPLONGHOST) $(NINITHOST) oracle
 
 $(LIB): $(SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(SRCS) -lrccl
@@ -81,11 +82,17 @@ $(CPHOST): tests/chachapoly_host.cpp grapevine_amd/csrc/gvs_chachapoly.h grapevi
 $(CPLONGHOST): tests/chachapoly_long_host.cpp grapevine_amd/csrc/gvs_chachapoly_long.h grapevine_amd/csrc/gvs_chachapoly.h grapevine_amd/csrc/gvs_chacha_rounds.h grapevine_amd/csrc/gvs_aead_long.h grapevine_amd/csrc/gvs_aead.h grapevine_amd/csrc/gvs_seal_dev.h grapevine_amd/csrc/gvs_crypto.h grapevine_amd/csrc/gvs_device.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/chachapoly_long_host.cpp
 
+# the device Noise IX initiator (the four phases of k_noise_ixi over four lane
+# states, chained with the host ladder and the serial ciphers) built for the
+# CPU (tests/test_noise_init.py)
+$(NINITHOST): tests/noise_init_host.cpp tests/noise_host.cpp tests/aead_host.cpp $(wildcard grapevine_amd/csrc/*.h)
+	$(HIPCC) -O2 -std=c++17 -fPIC -shared --offload-arch=$(ARCH) -o $@ tests/noise_init_host.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) $(CPLONGHOST)
+	rm -f $(LIB) $(TESTLIB) $(SRHOST) $(EDHOST) $(CHACHAHOST) $(AEADHOST) $(AEADLONGHOST) $(XHOST) $(NHOST) $(NLONGHOST) $(CPHOST) $(CPLONGHOST) $(NINITHOST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -116,6 +116,18 @@ _vp, _u32 = ctypes.c_void_p, ctypes.c_uint32
 # device form)
 NOISE_IX_RESPOND_ARGTYPES = [_vp, ctypes.c_char_p, ctypes.c_char_p, _u32, _vp, _vp, _u32, _vp, _vp, _u32,
                              _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]
+# the Noise IX initiator: the handshake hash that gvs_noise_ix_initiate hands to gvs_noise_ix_finish
+NOISE_INIT_STATE_BYTES = 64
+# h, cipher, prologue, prologue_len, statics, static_stride, ephemerals,
+# payload, payload_stride, payload_len, n, msg1, msg1_stride, msg1_lens,
+# states (gvs_noise_ix_initiate and its device form)
+NOISE_IX_INITIATE_ARGTYPES = [_vp, _u32, ctypes.c_char_p, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32,
+                              _vp, _vp]
+# h, cipher, statics, static_stride, ephemerals, states, msg2, msg2_stride,
+# msg2_lens, n, remote_statics, payload2, payload2_stride, payload2_lens,
+# send_keys, recv_keys, hashes, ok (gvs_noise_ix_finish and its device form)
+NOISE_IX_FINISH_ARGTYPES = [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp,
+                            _vp, _vp]
 
 
 def noise_iv(counter):

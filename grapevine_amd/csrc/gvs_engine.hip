@@ -41,6 +41,7 @@
 #include "gvs_chachapoly.h"
 #include "gvs_chachapoly_long.h"
 #include "gvs_noise_long.h"
+#include "gvs_noise_init.h"
 #include "gvs_spass.h"
 #include "gvs_mauth.h"
 #ifndef GVS_MA_EXTRA_LDS
@@ -3470,6 +3471,283 @@ int gvs_noise_ix_respond_long_cipher(gvs_handle* h, uint32_t cipher, const uint8
   return noise_ix_host(h, NoiseIxCall{static_secret, prologue, prologue_len, ephemerals, msg1, msg1_stride, msg1_lens,
                                       payload, payload_stride, payload_len, n, msg2, msg2_stride, msg2_lens,
                                       recv_keys, send_keys, hashes, ok, true, cipher});
+}
+
+// ------------------------------- the Noise IX initiator (gvs_noise_init.h)
+
+// An array of a host form on its way through the device scratch: up before
+// the chain (in), down after it (out).  dev is the call's pointer, rewritten.
+struct NoiseCol {
+  void* dev;  // the address of the call's pointer
+  size_t bytes;
+  bool out;
+};
+
+// The host forms of both calls: the chain's work area first, then the caller's
+// arrays in 16-byte-aligned parts; `run` is the chain on device pointers.
+static int noise_init_staged(gvs_handle* h, size_t work, std::vector<NoiseCol> cols, const std::function<int()>& run) {
+  size_t all = work;
+  for (const NoiseCol& c : cols) all += up16(c.bytes);
+  if (int r = dev_scratch(h, all)) return r;
+  if (int r = bounce_begin(h)) return r;
+  std::vector<void*> host;
+  uint8_t* d = h->sr_dev + work;
+  std::vector<uint8_t*> dev;
+  for (const NoiseCol& c : cols) {
+    void* hp;
+    std::memcpy(&hp, c.dev, sizeof hp);
+    host.push_back(hp);
+    dev.push_back(d);
+    if (!hp) continue;  // an optional array that was not passed
+    if (!c.out)
+      if (int r = h2d(h, d, hp, c.bytes)) return r;
+    std::memcpy(c.dev, &d, sizeof d);
+    d += up16(c.bytes);
+  }
+  if (int r = run()) return bounce_done(h, r);
+  for (size_t k = 0; k < cols.size(); ++k)
+    if (cols[k].out && host[k])
+      if (int r = d2h(h, host[k], dev[k], cols[k].bytes)) return r;
+  GVS_HIP(h, hipStreamSynchronize(h->stream));
+  return bounce_done(h, GVS_OK);
+}
+
+struct NoiseInitCall {
+  uint32_t cipher;
+  const uint8_t* prologue;  // host memory
+  uint32_t prologue_len;
+  const uint8_t* statics;   // the caller's arrays from here on: host memory (host) or device memory
+  uint32_t static_stride;
+  const uint8_t *eph, *payload;
+  uint32_t payload_stride, payload_len, n;
+  uint8_t* msg1;
+  uint32_t msg1_stride;
+  uint32_t* msg1_lens;
+  uint8_t* states;
+};
+
+// gvs_noise_ix_initiate and its device form: the scalars into one array, one
+// k_x25519 on the base point over n + (1 or n) items, k_noise_ixi<M1>
+static int noise_init(gvs_handle* h, NoiseInitCall c, bool host) {
+  if (!h || c.cipher > GVS_CIPHER_CHACHAPOLY || c.prologue_len > sr::kNxPrologueMax ||
+      (c.prologue_len && !c.prologue) || (c.static_stride && c.static_stride < 32) ||
+      c.payload_len > sr::kNxPayload1Max || (c.payload_len && !c.payload) ||
+      (c.payload_stride && c.payload_stride < c.payload_len) ||
+      (uint64_t)c.msg1_stride < 64ull + c.payload_len || c.n > max_submit(h) ||
+      (c.n && (!c.statics || !c.eph || !c.msg1 || !c.msg1_lens || !c.states)))
+    return GVS_ERR_INVALID_ARG;
+  if (!c.n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const uint32_t n = c.n;
+  const size_t rows = (size_t)n + (c.static_stride ? n : 1), work = 2 * rows * 32 + 64;
+  auto run = [&]() -> int {
+    uint8_t *xsc = h->sr_dev, *xout = xsc + rows * 32, *pro = xout + rows * 32;
+    sr::NxiScalarArgs g{};
+    if (c.prologue_len) std::memcpy(g.pro, c.prologue, c.prologue_len);
+    g.eph = c.eph, g.statics = c.statics, g.static_stride = c.static_stride, g.n = n, g.xsc = xsc, g.pro_out = pro;
+    sr::NxiArgs a{};
+    a.n = n, a.s_rows = c.static_stride ? 1u : 0u, a.pro = pro, a.pro_len = c.prologue_len;
+    a.payload = c.payload, a.payload_stride = c.payload_stride, a.payload_len = c.payload_len;
+    a.msg1 = c.msg1, a.msg1_stride = c.msg1_stride, a.msg1_lens = c.msg1_lens, a.states = c.states, a.xout = xout;
+    const dim3 grid((n + sr::kXItems - 1) / sr::kXItems), block(sr::kXThreads);
+    h->n_marks = 0;
+    mark(h, "start");
+    hipLaunchKernelGGL(sr::k_noise_ixi_scalars, dim3((uint32_t)((rows + sr::kXThreads - 1) / sr::kXThreads)), block, 0,
+                       h->stream, g);
+    enqueue_x25519(h, sr::XArgs{xsc, 32, nullptr, 0, (uint32_t)rows, xout, 32, nullptr});
+    mark(h, "x25519");
+    if (c.cipher == GVS_CIPHER_CHACHAPOLY)
+      hipLaunchKernelGGL((sr::k_noise_ixi<sr::kNxiM1, true>), grid, block, 0, h->stream, a);
+    else
+      hipLaunchKernelGGL((sr::k_noise_ixi<sr::kNxiM1, false>), grid, block, 0, h->stream, a);
+    mark(h, "noise_m1");
+    GVS_HIP(h, hipGetLastError());
+    GVS_HIP(h, hipStreamSynchronize(h->stream));
+    return GVS_OK;
+  };
+  if (!host) {
+    if (int r = dev_scratch(h, work)) return r;
+    return run();
+  }
+  return noise_init_staged(
+      h, work,
+      {{&c.statics, c.static_stride ? (size_t)(n - 1) * c.static_stride + 32 : 32, false},
+       {&c.eph, (size_t)n * 32, false},
+       {&c.payload, c.payload_len ? (c.payload_stride ? (size_t)(n - 1) * c.payload_stride : 0) + c.payload_len : 0, false},
+       {&c.msg1, (size_t)n * c.msg1_stride, true},
+       {&c.msg1_lens, (size_t)n * 4, true},
+       {&c.states, (size_t)n * 64, true}},
+      run);
+}
+
+struct NoiseFinishCall {
+  uint32_t cipher;
+  const uint8_t* statics;  // the caller's arrays: host memory (host) or device memory
+  uint32_t static_stride;
+  const uint8_t *eph, *states, *msg2;
+  uint32_t msg2_stride;
+  const uint32_t* msg2_lens;
+  uint32_t n;
+  uint8_t *rs, *payload2;
+  uint32_t payload2_stride;
+  uint32_t* payload2_lens;
+  uint8_t *send, *recv, *hashes;
+  uint32_t* ok;
+};
+
+// ct_p's rows in the work area: whole blocks, as long as the longest message 2
+// that the slots and the short form allow
+static uint32_t noise_finish_ct2(const NoiseFinishCall& c) {
+  const uint32_t m2 = std::min<uint32_t>(c.msg2_stride, sr::kNxMsg2Fixed + sr::kNxiPayload2Max);
+  return (uint32_t)up16(m2 - 80);
+}
+
+static size_t noise_finish_work_bytes(const NoiseFinishCall& c) {
+  const size_t n = c.n, c2 = noise_finish_ct2(c);
+  return 3 * 2 * n * 32 + up16(2 * n * 4) + n * 32 + n * (128 + 32 + 64 + 48 + 32 + c2 + c2) + up16(n * 12) +
+         8 * up16(n * 4);
+}
+
+// gvs_noise_ix_finish and its device form: the gather, k_x25519 over 2n items
+// (ee, se), k_noise_ixi<A>, the open of ct_s, k_x25519 over n items (es on what
+// it opened to), k_noise_ixi<B>, the open of ct_p, k_noise_ixi<C>
+static int noise_finish(gvs_handle* h, NoiseFinishCall c, bool host) {
+  if (!h || c.cipher > GVS_CIPHER_CHACHAPOLY || (c.static_stride && c.static_stride < 32) ||
+      c.msg2_stride < sr::kNxMsg2Fixed || c.n > max_submit(h) || (c.payload2_stride && !c.payload2) ||
+      (c.n && (!c.statics || !c.eph || !c.states || !c.msg2 || !c.msg2_lens || !c.rs || !c.payload2_lens ||
+               !c.send || !c.recv || !c.ok)))
+    return GVS_ERR_INVALID_ARG;
+  if (!c.n) return GVS_OK;
+  GVS_HIP(h, hipSetDevice(h->device));
+  const uint32_t n = c.n, c2 = noise_finish_ct2(c);
+  const size_t work = noise_finish_work_bytes(c);
+  auto run = [&]() -> int {
+    const bool cp = c.cipher == GVS_CIPHER_CHACHAPOLY;
+    if (!cp)
+      if (int r = aead_init(h)) return r;
+    uint8_t* p = h->sr_dev;
+    auto take = [&](size_t bytes) {
+      uint8_t* q = p;
+      p += up16(bytes);
+      return q;
+    };
+    const size_t x = 2 * (size_t)n;
+    uint8_t *xsc = take(x * 32), *xpt = take(x * 32), *xout = take(x * 32);
+    uint32_t* xok = (uint32_t*)take(x * 4);
+    uint8_t *xout3 = take((size_t)n * 32), *st = take((size_t)n * 128), *key = take((size_t)n * 32),
+            *aad = take((size_t)n * 64), *ct1 = take((size_t)n * 48), *pt1 = take((size_t)n * 32),
+            *ct2 = take((size_t)n * c2), *pt2 = take((size_t)n * c2);
+    uint32_t* iv = (uint32_t*)take((size_t)n * 12);
+    uint32_t *aad_lens = (uint32_t*)take((size_t)n * 4), *len1 = (uint32_t*)take((size_t)n * 4),
+             *len2 = (uint32_t*)take((size_t)n * 4), *olens = (uint32_t*)take((size_t)n * 4),
+             *ok1 = (uint32_t*)take((size_t)n * 4), *ok2 = (uint32_t*)take((size_t)n * 4),
+             *xok3 = (uint32_t*)take((size_t)n * 4);
+
+    sr::NxiGatherArgs g{};
+    g.eph = c.eph, g.statics = c.statics, g.static_stride = c.static_stride;
+    g.msg2 = c.msg2, g.msg2_stride = c.msg2_stride, g.msg2_lens = c.msg2_lens;
+    g.payload2_stride = c.payload2_stride, g.ct2_stride = c2, g.n = n;
+    g.xsc = xsc, g.xpt = xpt, g.ct1 = ct1, g.ct2 = ct2, g.iv = iv, g.aad_lens = aad_lens, g.len1 = len1, g.len2 = len2;
+
+    sr::NxiArgs a{};
+    a.n = n, a.states = const_cast<uint8_t*>(c.states), a.xout = xout, a.xok = xok, a.xout3 = xout3, a.xok3 = xok3;
+    a.msg2 = c.msg2, a.msg2_stride = c.msg2_stride, a.msg2_lens = c.msg2_lens;
+    a.st = st, a.key = key, a.aad = aad, a.ct1 = ct1, a.ct2 = ct2, a.ct2_stride = c2;
+    a.pt1 = pt1, a.pt2 = pt2, a.pt2_stride = c2, a.ok1 = ok1, a.ok2 = ok2;
+    a.rs = c.rs, a.payload2 = c.payload2, a.payload2_stride = c.payload2_stride, a.payload2_lens = c.payload2_lens;
+    a.send = c.send, a.recv = c.recv, a.hashes = c.hashes, a.ok = c.ok;
+
+    AeadArgs o1{};
+    o1.keys = (const uint4*)key, o1.ivs = iv, o1.aad = aad, o1.aad_stride = 64, o1.aad_lens = aad_lens;
+    o1.in = ct1, o1.in_stride = 48, o1.in_lens = len1, o1.n = n;
+    o1.out = pt1, o1.out_stride = 32, o1.out_lens = olens, o1.ok = ok1;
+    AeadArgs o2 = o1;
+    o2.in = ct2, o2.in_stride = c2, o2.in_lens = len2, o2.out = pt2, o2.out_stride = c2, o2.ok = ok2;
+
+    const dim3 grid((n + sr::kXItems - 1) / sr::kXItems), block(sr::kXThreads);
+    h->n_marks = 0;
+    mark(h, "start");
+    hipLaunchKernelGGL(sr::k_noise_ixi_gather, grid, block, 0, h->stream, g);
+    enqueue_x25519(h, sr::XArgs{xsc, 32, xpt, 32, (uint32_t)x, xout, 32, xok});
+    mark(h, "x25519");
+    if (cp)
+      hipLaunchKernelGGL((sr::k_noise_ixi<sr::kNxiA, true>), grid, block, 0, h->stream, a);
+    else
+      hipLaunchKernelGGL((sr::k_noise_ixi<sr::kNxiA, false>), grid, block, 0, h->stream, a);
+    mark(h, "noise_ia");
+    enqueue_cipher(h, c.cipher, false, o1);
+    enqueue_x25519(h, sr::XArgs{c.eph, 32, pt1, 32, n, xout3, 32, xok3});
+    mark(h, "x25519_es");
+    hipLaunchKernelGGL((sr::k_noise_ixi<sr::kNxiB>), grid, block, 0, h->stream, a);
+    mark(h, "noise_ib");
+    enqueue_cipher(h, c.cipher, false, o2);
+    hipLaunchKernelGGL((sr::k_noise_ixi<sr::kNxiC>), grid, block, 0, h->stream, a);
+    mark(h, "noise_ic");
+    GVS_HIP(h, hipGetLastError());
+    GVS_HIP(h, hipStreamSynchronize(h->stream));
+    return GVS_OK;
+  };
+  if (!host) {
+    if (int r = dev_scratch(h, work)) return r;
+    return run();
+  }
+  const size_t b32 = (size_t)n * 32;
+  return noise_init_staged(
+      h, work,
+      {{&c.statics, c.static_stride ? (size_t)(n - 1) * c.static_stride + 32 : 32, false},
+       {&c.eph, b32, false},
+       {&c.states, (size_t)n * 64, false},
+       {&c.msg2, (size_t)n * c.msg2_stride, false},
+       {&c.msg2_lens, (size_t)n * 4, false},
+       {&c.rs, b32, true},
+       {&c.payload2, (size_t)n * c.payload2_stride, true},
+       {&c.payload2_lens, (size_t)n * 4, true},
+       {&c.send, b32, true},
+       {&c.recv, b32, true},
+       {&c.hashes, (size_t)n * 64, true},
+       {&c.ok, (size_t)n * 4, true}},
+      run);
+}
+
+int gvs_noise_ix_initiate(gvs_handle* h, uint32_t cipher, const uint8_t* prologue, uint32_t prologue_len,
+                          const uint8_t* statics, uint32_t static_stride, const uint8_t* ephemerals,
+                          const uint8_t* payload, uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                          uint8_t* msg1, uint32_t msg1_stride, uint32_t* msg1_lens, uint8_t* states) {
+  return noise_init(h, NoiseInitCall{cipher, prologue, prologue_len, statics, static_stride, ephemerals, payload,
+                                     payload_stride, payload_len, n, msg1, msg1_stride, msg1_lens, states}, true);
+}
+
+int gvs_noise_ix_initiate_device(gvs_handle* h, uint32_t cipher, const uint8_t* prologue, uint32_t prologue_len,
+                                 const void* d_statics, uint32_t static_stride, const void* d_ephemerals,
+                                 const void* d_payload, uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                                 void* d_msg1, uint32_t msg1_stride, uint32_t* d_msg1_lens, void* d_states) {
+  return noise_init(h, NoiseInitCall{cipher, prologue, prologue_len, (const uint8_t*)d_statics, static_stride,
+                                     (const uint8_t*)d_ephemerals, (const uint8_t*)d_payload, payload_stride,
+                                     payload_len, n, (uint8_t*)d_msg1, msg1_stride, d_msg1_lens, (uint8_t*)d_states},
+                    false);
+}
+
+int gvs_noise_ix_finish(gvs_handle* h, uint32_t cipher, const uint8_t* statics, uint32_t static_stride,
+                        const uint8_t* ephemerals, const uint8_t* states, const uint8_t* msg2, uint32_t msg2_stride,
+                        const uint32_t* msg2_lens, uint32_t n, uint8_t* remote_statics, uint8_t* payload2,
+                        uint32_t payload2_stride, uint32_t* payload2_lens, uint8_t* send_keys, uint8_t* recv_keys,
+                        uint8_t* hashes, uint32_t* ok) {
+  return noise_finish(h, NoiseFinishCall{cipher, statics, static_stride, ephemerals, states, msg2, msg2_stride,
+                                         msg2_lens, n, remote_statics, payload2, payload2_stride, payload2_lens,
+                                         send_keys, recv_keys, hashes, ok}, true);
+}
+
+int gvs_noise_ix_finish_device(gvs_handle* h, uint32_t cipher, const void* d_statics, uint32_t static_stride,
+                               const void* d_ephemerals, const void* d_states, const void* d_msg2,
+                               uint32_t msg2_stride, const uint32_t* d_msg2_lens, uint32_t n, void* d_remote_statics,
+                               void* d_payload2, uint32_t payload2_stride, uint32_t* d_payload2_lens,
+                               void* d_send_keys, void* d_recv_keys, void* d_hashes, uint32_t* d_ok) {
+  return noise_finish(h, NoiseFinishCall{cipher, (const uint8_t*)d_statics, static_stride,
+                                         (const uint8_t*)d_ephemerals, (const uint8_t*)d_states,
+                                         (const uint8_t*)d_msg2, msg2_stride, d_msg2_lens, n,
+                                         (uint8_t*)d_remote_statics, (uint8_t*)d_payload2, payload2_stride,
+                                         d_payload2_lens, (uint8_t*)d_send_keys, (uint8_t*)d_recv_keys,
+                                         (uint8_t*)d_hashes, d_ok}, false);
 }
 
 // ---------------------------------------------------- channel cipher alone

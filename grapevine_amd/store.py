@@ -49,6 +49,7 @@ EXPORTED = (
     "gvs_chachapoly_open_long", "gvs_chachapoly_open_long_device",
     "gvs_chachapoly_seal_long", "gvs_chachapoly_seal_long_device",
     "gvs_noise_ix_respond_long_cipher", "gvs_noise_ix_respond_long_cipher_device",
+    "gvs_noise_ix_initiate", "gvs_noise_ix_initiate_device", "gvs_noise_ix_finish", "gvs_noise_ix_finish_device",
 )
 TEST_EXPORTED = ("gvs_dump_messages", "gvs_raw_size", "gvs_dump_raw", "gvs_store_raw",
                  "gvs_route_plan", "gvs_oram_test_handle", "gvs_omap_test_handle", "gvs_test_set_epoch")
@@ -129,6 +130,8 @@ def load_library(path=None):
         [vp, u32] + abi.NOISE_IX_RESPOND_ARGTYPES[1:]
     lib.gvs_noise_ix_respond_long_cipher.argtypes = lib.gvs_noise_ix_respond_long_cipher_device.argtypes = \
         lib.gvs_noise_ix_respond_cipher.argtypes
+    lib.gvs_noise_ix_initiate.argtypes = lib.gvs_noise_ix_initiate_device.argtypes = abi.NOISE_IX_INITIATE_ARGTYPES
+    lib.gvs_noise_ix_finish.argtypes = lib.gvs_noise_ix_finish_device.argtypes = abi.NOISE_IX_FINISH_ARGTYPES
     lib.gvs_wire_decode_device.argtypes =[vp, vp, u32, vp, u32, vp, vp, vp, vp]
     lib.gvs_wire_encode_device.argtypes = [vp, vp, u32, vp, u32, vp]
     lib.gvs_process_batches.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(u32)]
@@ -713,6 +716,98 @@ class ObliviousStore:
     def noise_ix_respond_long_device(self, *args, **kw):
         """noise_ix_respond_device(..., long=True)."""
         self.noise_ix_respond_device(*args, long=True, **kw)
+
+    def noise_ix_initiate(self, statics, ephemerals, payload=b"", prologue=b"", msg1_stride=None, cipher=None,
+                          device=False, out=None):
+        """The initiator's message 1 of n Noise IX handshakes on the device
+        (gvs_noise_ix_initiate): statics 32 bytes (one static secret for all)
+        or (n, 32), ephemerals (n, 32) fresh secrets, payload one byte string
+        for all or a list of n of one length (<= abi.NOISE_PAYLOAD1_MAX),
+        prologue bytes -> (list of n first messages, states (n, 64), the
+        (n, stride) message-1 slab).  cipher: abi.CIPHER_AESGCM (None) or
+        abi.CIPHER_CHACHAPOLY.  device=True is gvs_noise_ix_initiate_device on
+        torch CUDA tensors: statics (32,) or (n, >= 32), ephemerals (n, 32),
+        payload None, 1-D (one for all) or (n, >= its length); out = (msg1
+        (n, stride) uint8, msg1_lens (n,) int32, states (n, 64)) is written in
+        place (made when None) and returned; the caller synchronises its own
+        streams first."""
+        cipher = abi.CIPHER_AESGCM if cipher is None else cipher
+        if device:
+            import torch
+            n = ephemerals.shape[0]
+            plen = 0 if payload is None else payload.shape[-1]
+            if out is None:
+                kw = dict(device=ephemerals.device)
+                out = (torch.zeros((n, msg1_stride or 64 + plen), dtype=torch.uint8, **kw),
+                       torch.zeros(n, dtype=torch.int32, **kw), torch.zeros((n, 64), dtype=torch.uint8, **kw))
+            msg1, lens, states = out
+            self._check(self.lib.gvs_noise_ix_initiate_device(
+                self.h, cipher, bytes(prologue), len(prologue), statics.data_ptr(),
+                0 if statics.dim() == 1 else statics.stride(0), ephemerals.data_ptr(),
+                payload.data_ptr() if plen else None, 0 if payload is None or payload.dim() == 1 else payload.stride(0),
+                plen, n, msg1.data_ptr(), msg1.stride(0), lens.data_ptr(), states.data_ptr()))
+            return out
+        eph = np.ascontiguousarray(ephemerals, np.uint8).reshape(-1, 32)
+        n = len(eph)
+        st = np.frombuffer(bytes(statics), np.uint8) if isinstance(statics, (bytes, bytearray)) else \
+            np.ascontiguousarray(statics, np.uint8).reshape(n, 32)
+        one = isinstance(payload, (bytes, bytearray))
+        pays = [bytes(payload)] if one else [bytes(p) for p in payload]
+        plen = len(pays[0]) if pays else 0
+        if any(len(p) != plen for p in pays) or (not one and len(pays) != n):
+            raise ValueError("noise_ix_initiate: one payload length per call")
+        pay = np.frombuffer(b"".join(pays), np.uint8) if plen else None
+        stride = msg1_stride if msg1_stride is not None else 64 + plen
+        msg1, lens, states = np.zeros((n, max(stride, 1)), np.uint8), np.zeros(n, np.uint32), np.zeros((n, 64), np.uint8)
+        self._check(self.lib.gvs_noise_ix_initiate(
+            self.h, cipher, bytes(prologue), len(prologue), st.ctypes.data, 0 if st.ndim == 1 else 32,
+            eph.ctypes.data, pay.ctypes.data if pay is not None else None, 0 if one else plen, plen, n,
+            msg1.ctypes.data, stride, lens.ctypes.data, states.ctypes.data))
+        return [msg1[k, :lens[k]].tobytes() for k in range(n)], states, msg1
+
+    def noise_ix_finish(self, statics, ephemerals, states, msg2, msg2_lens=None, payload2_stride=None, cipher=None,
+                        device=False, out=None):
+        """The initiator's reading of message 2 (gvs_noise_ix_finish; payload
+        2 <= abi.AEAD_TEXT_MAX bytes): statics, ephemerals and cipher as in
+        `noise_ix_initiate`, states what it returned, msg2 a list of n second
+        messages -> (remote statics (n, 32), list of n payloads, send_keys
+        (n, 32), recv_keys (n, 32), hashes (n, 64), (n,) bool, the (n, stride)
+        payload slab).  A handshake that fails is all zero with b"".
+        device=True is gvs_noise_ix_finish_device on torch CUDA tensors: msg2
+        (n, stride >= 96) uint8 with msg2_lens (n,) int32; out =
+        (remote_statics, payload2 (n, stride), payload2_lens, send_keys,
+        recv_keys, hashes, ok) is written in place (made when None) and
+        returned."""
+        cipher = abi.CIPHER_AESGCM if cipher is None else cipher
+        if device:
+            import torch
+            n = msg2.shape[0]
+            if out is None:
+                u8 = lambda w: torch.zeros((n, w), dtype=torch.uint8, device=msg2.device)
+                i32 = lambda: torch.zeros(n, dtype=torch.int32, device=msg2.device)
+                p2s = payload2_stride if payload2_stride is not None else max(msg2.stride(0) - 96, 1)
+                out = (u8(32), u8(p2s), i32(), u8(32), u8(32), u8(64), i32())
+            rs, pay, plens, sk, rk, hh, ok = out
+            self._check(self.lib.gvs_noise_ix_finish_device(
+                self.h, cipher, statics.data_ptr(), 0 if statics.dim() == 1 else statics.stride(0),
+                ephemerals.data_ptr(), states.data_ptr(), msg2.data_ptr(), msg2.stride(0), msg2_lens.data_ptr(), n,
+                rs.data_ptr(), pay.data_ptr(), pay.stride(0), plens.data_ptr(), sk.data_ptr(), rk.data_ptr(),
+                hh.data_ptr() if hh is not None else None, ok.data_ptr()))
+            return out
+        eph = np.ascontiguousarray(ephemerals, np.uint8).reshape(-1, 32)
+        n = len(eph)
+        st = np.frombuffer(bytes(statics), np.uint8) if isinstance(statics, (bytes, bytearray)) else \
+            np.ascontiguousarray(statics, np.uint8).reshape(n, 32)
+        states = np.ascontiguousarray(states, np.uint8).reshape(n, 64)
+        slab, lens, stride = self._wire_slab(msg2, max([len(m) for m in msg2] + [96]))
+        p2s = payload2_stride if payload2_stride is not None else max(stride - 96, 1)
+        pay, plens, ok = np.zeros((n, p2s), np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        rs, sk, rk, hh = (np.zeros((n, w), np.uint8) for w in (32, 32, 32, 64))
+        self._check(self.lib.gvs_noise_ix_finish(
+            self.h, cipher, st.ctypes.data, 0 if st.ndim == 1 else 32, eph.ctypes.data, states.ctypes.data,
+            slab.ctypes.data, stride, lens.ctypes.data, n, rs.ctypes.data, pay.ctypes.data, p2s, plens.ctypes.data,
+            sk.ctypes.data, rk.ctypes.data, hh.ctypes.data, ok.ctypes.data))
+        return rs, [pay[k, :plens[k]].tobytes() for k in range(n)], sk, rk, hh, ok.astype(bool), pay
 
     def access(self, req):
         out = self.process_batch(np.asarray([req], dtype=abi.REQUEST_DTYPE) if not isinstance(req, np.ndarray) else req.reshape(1))

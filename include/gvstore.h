@@ -738,6 +738,65 @@ int gvs_noise_ix_respond_long_cipher_device(gvs_handle *h, uint32_t cipher,
                                             uint32_t *d_msg2_lens, void *d_recv_keys,
                                             void *d_send_keys, void *d_hashes, uint32_t *d_ok);
 
+/* The initiator's side of the same handshakes, batched: n clients (or one
+ * broker towards n peers) in two calls around the responder's message 2.
+ * cipher is GVS_CIPHER_AESGCM or GVS_CIPHER_CHACHAPOLY.  Every array of the
+ * host forms is host memory and every array of the _device forms device
+ * memory, the static secrets included; only the prologue is host memory in
+ * both.  Both calls are synchronous on the handle's stream; n = 0 is a no-op.
+ *
+ * gvs_noise_ix_initiate writes message 1 (-> e, s): handshake k uses the
+ * static secret at statics + k * static_stride (static_stride 0: one secret
+ * for all, else >= 32), the fresh ephemeral secret ephemerals[k] (32 bytes
+ * from the caller's CSPRNG) and payload 1 at payload + k * payload_stride
+ * (payload_stride 0: one for all; payload_len <= GVS_NOISE_PAYLOAD1_MAX).
+ * Slot k of msg1 (msg1_stride >= 64 + payload_len apart) is written whole:
+ * e_pub | s_pub | payload, then zeros; msg1_lens[k] = 64 + payload_len, and
+ * states[k] (GVS_NOISE_INIT_STATE_BYTES) is the handshake hash after message
+ * 1, which gvs_noise_ix_finish takes back with the same secrets.
+ *
+ * gvs_noise_ix_finish reads message 2 (<- e, ee, se, s, es) = re 32 | ct_s 48
+ * | ct_p from slot k of msg2 (msg2_stride >= 96 apart), msg2_lens[k] bytes of
+ * it.  This is the short form: payload 2 has at most GVS_AEAD_TEXT_MAX bytes.
+ * It returns the responder's static public key in remote_statics[k], payload
+ * 2 in slot k of payload2 (payload2_stride apart, written whole) with its
+ * length in payload2_lens[k], send_keys[k] (initiator to responder: what the
+ * responder's call returns as recv_keys), recv_keys[k] (the other direction)
+ * and the handshake hash in hashes[k] (hashes may be NULL).  Handshake k gets
+ * ok[k] = 0, zero keys, hash and remote static, a zeroed payload slot and
+ * length 0 for a message 2 shorter than 96 bytes, longer than 96 +
+ * GVS_AEAD_TEXT_MAX, than its slot or than 96 + payload2_stride, for an
+ * all-zero ee, se or es, and for a ciphertext that fails its tag; its
+ * neighbours are not affected.  GVS_ERR_INVALID_ARG is for the call's own
+ * arguments: another cipher, a length or stride outside the limits above, a
+ * missing array. */
+#define GVS_NOISE_INIT_STATE_BYTES 64
+int gvs_noise_ix_initiate(gvs_handle *h, uint32_t cipher, const uint8_t *prologue,
+                          uint32_t prologue_len, const uint8_t *statics, uint32_t static_stride,
+                          const uint8_t *ephemerals, const uint8_t *payload,
+                          uint32_t payload_stride, uint32_t payload_len, uint32_t n,
+                          uint8_t *msg1, uint32_t msg1_stride, uint32_t *msg1_lens,
+                          uint8_t *states);
+int gvs_noise_ix_initiate_device(gvs_handle *h, uint32_t cipher, const uint8_t *prologue,
+                                 uint32_t prologue_len, const void *d_statics,
+                                 uint32_t static_stride, const void *d_ephemerals,
+                                 const void *d_payload, uint32_t payload_stride,
+                                 uint32_t payload_len, uint32_t n, void *d_msg1,
+                                 uint32_t msg1_stride, uint32_t *d_msg1_lens, void *d_states);
+int gvs_noise_ix_finish(gvs_handle *h, uint32_t cipher, const uint8_t *statics,
+                        uint32_t static_stride, const uint8_t *ephemerals, const uint8_t *states,
+                        const uint8_t *msg2, uint32_t msg2_stride, const uint32_t *msg2_lens,
+                        uint32_t n, uint8_t *remote_statics, uint8_t *payload2,
+                        uint32_t payload2_stride, uint32_t *payload2_lens, uint8_t *send_keys,
+                        uint8_t *recv_keys, uint8_t *hashes, uint32_t *ok);
+int gvs_noise_ix_finish_device(gvs_handle *h, uint32_t cipher, const void *d_statics,
+                               uint32_t static_stride, const void *d_ephemerals,
+                               const void *d_states, const void *d_msg2, uint32_t msg2_stride,
+                               const uint32_t *d_msg2_lens, uint32_t n, void *d_remote_statics,
+                               void *d_payload2, uint32_t payload2_stride,
+                               uint32_t *d_payload2_lens, void *d_send_keys, void *d_recv_keys,
+                               void *d_hashes, uint32_t *d_ok);
+
 /* Message expiry (README.md:86-99: the untrusted host supplies the time and
  * the expiry period).  From the next batch on, messages whose timestamp is
  * < cutoff expire: each batch's message pass records up to X of them (fixed
